@@ -380,8 +380,32 @@ def injection_case():
     save("syn_generator_inject.npz", **out)
 
 
+def noise_pool_case():
+    """syn_noise_random.npz: the reference Generator of syn_generator_none.npz with every noise_strength 0.3, synthesis(ws_psi1,
+    noise_mode='random') under torch.manual_seed(11) — each layer draws its own torch.randn (networks_stylegan2.py:342) — and how far
+    the planes of seed 12 lie from it (tests/test_host_cpu.py::test_noise_pool_off_reproduces_the_references_random_draws)."""
+    g = np.load(os.path.join(HERE, "syn_generator_none.npz"))
+    kw = dict(z_dim=64, c_dim=25, w_dim=64, img_resolution=32, img_channels=96, mapping_kwargs={"num_layers": 2},
+              channel_base=2048, channel_max=64, num_fp16_res=0, conv_clamp=None, fused_modconv_default="inference_only")
+    G = ns.Generator(cond_mode="none", **kw).eval()
+    G.load_state_dict({k[3:].replace("__", "."): torch.from_numpy(v) for k, v in g.items() if k.startswith("sd_")}, strict=True)
+    for n, p_ in G.named_parameters():
+        if n.endswith("noise_strength"):
+            p_.fill_(0.3)
+    ws = torch.from_numpy(g["ws_psi1"])
+    torch.manual_seed(11)
+    want = G.synthesis(ws, {}, noise_mode="random")
+    torch.manual_seed(12)
+    other = G.synthesis(ws, {}, noise_mode="random")
+    save("syn_noise_random.npz", planes_seed11=want.numpy(), max_abs_seed12_vs_seed11=np.float64((want - other).abs().max()),
+         torch_version=np.array(torch.__version__))
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
+    if sys.argv[1:] == ["noise"]:
+        noise_pool_case()
+        sys.exit(0)
     if sys.argv[1:] == ["inject"]:  # only the fixtures added at the end of round 4
         injection_case()
         sys.exit(0)

@@ -1,5 +1,5 @@
-"""CPU, build container only (skipped where /root/reference is absent, e.g. on the GPU box): the drop-in EXECUTED against the
-reference's own tree, the way `_train/eg3dc/util/eg3dc_v0.py:47-52` re-instantiates a checkpoint:
+"""CPU: the drop-in EXECUTED against the reference's own tree (those tests skip where it is absent; the recorded layout of
+tests/golden/dropin_reference.npz stands in for (1) everywhere), the way `_train/eg3dc/util/eg3dc_v0.py:47-52` re-instantiates a checkpoint:
 
     G_new = TriPlaneGenerator(*G.init_args, **G.init_kwargs);  misc.copy_params_and_buffers(G, G_new, require_all=True)
 
@@ -16,7 +16,6 @@ import pytest
 import torch
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "_train", "eg3dc", "src")), reason="needs the reference tree")
 
 TRI_RK = {"image_resolution": 512, "disparity_space_sampling": False, "clamp_mode": "softplus",
           "superresolution_module": "training.superresolution.SuperresolutionHybrid8XDC", "c_gen_conditioning_zero": False,
@@ -34,6 +33,8 @@ KWS = [dict(z_dim=512, c_dim=25, w_dim=512, img_resolution=512, img_channels=3, 
 
 @pytest.fixture(scope="module")
 def ref_modules():
+    if not os.path.isdir(os.path.join(REF, "_train", "eg3dc", "src")):
+        pytest.skip("needs the reference tree")
     os.environ.setdefault("PROJECT_DN", REF)
     os.environ.setdefault("PROJECT_NAME", "x")
     added = [REF, os.path.join(REF, "_train", "eg3dc", "src")]
@@ -71,6 +72,26 @@ def test_reference_loader_recipe_on_our_generator(ref_modules, kw):
         assert callable(getattr(G_new, name))
     # and back: the reference's class accepts our state_dict unchanged (strict)
     G.load_state_dict(G_new.state_dict(), strict=True)
+
+
+@pytest.mark.parametrize("tag", ["uncond", "cond"])
+def test_loader_recipe_on_the_recorded_reference_generator(tag):
+    """The recipe above against what the reference's generator recorded and held for the same constructions
+    (tests/golden/dropin_reference.npz, tests/golden/make_golden_dropin.py): our class from the recorded init_args / init_kwargs has
+    the same parameters and buffers (names, shapes, order: what a copy by name with require_all needs), and the state_dict keys are
+    the reference's (a strict load either way)."""
+    import json
+    import numpy as np
+    import panic3d_amd
+    rec = json.loads(str(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dropin_reference.npz"))[tag]))
+    assert rec["init_kwargs"] == json.loads(json.dumps(KWS[("uncond", "cond").index(tag)]))  # the recorded arguments are the construction's
+    G_new = panic3d_amd.generator.TriPlaneGenerator(*rec["init_args"], **rec["init_kwargs"]).eval().requires_grad_(False)
+    new = [(n, list(t.shape)) for n, t in list(G_new.named_parameters()) + list(G_new.named_buffers())]
+    assert new == [tuple(x) for x in rec["params_and_buffers"]]  # same names, same shapes: nothing missing on either side
+    assert list(G_new.state_dict().keys()) == rec["state_dict"]
+    assert G_new.set_force_sigmoid(True) is True  # eg3dc_v0.py:54 (triplane.py:545)
+    for name in ("mapping", "mapping_zplus", "synthesis", "sample_mixed", "f"):  # the call surface generate.py / eg3d_metrics3d.py use
+        assert callable(getattr(G_new, name))
 
 
 def test_reference_generator_constructs_with_our_renderer(ref_modules, monkeypatch):

@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import pytest
 import torch
@@ -16,15 +17,27 @@ SMALL = ["--steps", "6", "--warmup", "2", "--roofline-steps", "3"]
 
 
 def _bench(args, launched):
+    """The full record (--details FILE), after checking the printed line: exactly one, short, and the record's summary."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable]
     if launched:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", "29561"]
-    r = subprocess.run(cmd + [os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
-    assert len(lines) == 1, r.stdout[-2000:]  # exactly one JSON line
-    return json.loads(lines[0])
+    with tempfile.TemporaryDirectory() as tmp:
+        details = os.path.join(tmp, "details.json")
+        r = subprocess.run(cmd + [os.path.join(ROOT, "bench.py")] + args + ["--details", details], capture_output=True, text=True, timeout=900,
+                           env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]  # exactly one JSON line
+        assert len(lines[0]) < 4096, len(lines[0])  # whole in any tail of the output
+        line = json.loads(lines[0])
+        d = json.load(open(details))
+    assert line["details"] == details
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "wsum_mean", "hit_fraction"):
+        assert line[k] == d[k], k
+    assert line["kernel_ms"] == d["roofline"]["kernel_ms"] and line["roofline"]["frac"] == d["roofline"]["frac"]
+    assert ("verify_ok" in line) == ("verify" in d) and line.get("verify_ok") == d.get("verify", {}).get("ok")
+    return d
 
 
 def _check_line(d, steps, scene="surface"):
@@ -164,3 +177,44 @@ def test_bench_views_per_step_renders_v_views_per_launch():
     r = d["roofline"]
     assert r["algorithmic_bytes_per_launch"] == 3 * 512 * 512 * (96 * 1536 + 172) and 0 < r["frac"] <= 1.0
     assert d["verify"]["ok"] is True and "3 views per GPU per step in ONE launch" in d["config"]["workload"]
+
+
+def _dump_run(tmp, run, extra=()):
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--roofline-steps", "0", "--no-table", "--no-pipeline", "--no-cpu-baseline", "--no-verify", *extra]
+    out = os.path.join(tmp, run)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", out], capture_output=True, text=True,
+                       timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert sorted(os.listdir(out)) == ["depth.npy", "feat.npy", "wsum.npy", "xyz.npy"]
+    return line, {n[:-4]: np.load(os.path.join(out, n)) for n in os.listdir(out)}
+
+
+def test_bench_dump_outputs_are_the_last_steps_and_repeat():
+    """`--dump-outputs DIR`: the arrays the timed step returned in its last step (feat, depth, wsum, xyz), float32, <= 16 MB; two runs
+    with the same arguments render the same inputs, so they dump the same bytes.  A 512^2 frame (38 MB) is dumped as one seeded sample
+    of rays taken from every array; a 256^2 frame whole, in the shapes the caller receives."""
+    import numpy as np
+    with tempfile.TemporaryDirectory() as tmp:
+        (la, a), (_, b) = _dump_run(tmp, "a"), _dump_run(tmp, "b")
+        ls, small = _dump_run(tmp, "small", ["--res", "256"])
+    assert la["steps"] == 3 and sum(x.nbytes for x in a.values()) <= 16 << 20
+    n = a["feat"].shape[0]
+    assert 0.25 * 512 * 512 < n < 512 * 512
+    for k, c in (("feat", 32), ("depth", 1), ("wsum", 1), ("xyz", 3)):
+        assert a[k].dtype == np.float32 and a[k].shape == (n, c) and np.array_equal(a[k], b[k]), k
+    assert abs(float(a["wsum"].astype(np.float64).mean()) - la["wsum_mean"]) < 0.02 and a["wsum"].max() > 0.5  # a sample of the frame
+    R = 256 * 256
+    for k, c in (("feat", 32), ("depth", 1), ("wsum", 1), ("xyz", 3)):
+        assert small[k].dtype == np.float32 and small[k].shape == (1, R, c), k
+    assert abs(float(small["wsum"].astype(np.float64).mean()) - ls["wsum_mean"]) < 1e-5  # the line's wsum_mean is the last step's
+
+
+def test_bench_side_tables_take_a_fixed_number_of_steps():
+    """`--steps K` sets the timed region; the side tables and the device_rng row take min(K, --table-steps) steps, so a run's wall
+    time is the K timed steps plus a fixed cost, whatever K is."""
+    d = _bench(["--steps", "40", "--warmup", "2", "--roofline-steps", "2", "--no-pipeline", "--no-cpu-baseline", "--no-verify"], launched=False)
+    assert d["steps"] == 40
+    assert all(r["steps"] == 20 for r in d["results"]) and all(r["steps"] == 10 for r in d["eval_faithful"]["rows"])
+    assert d["device_rng"]["steps"] == 20

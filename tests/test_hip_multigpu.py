@@ -45,8 +45,11 @@ def test_c5_grid_same_sigma_for_world_size_1_and_2():
     assert b["n_gpus"] == 2 and a["sha256"] == b["sha256"] and a["verts"] == b["verts"]
 
 
-def test_bench_two_ranks_prints_per_rank_times_and_verifies():
-    out = _run("bench.py", ["--gpus", "2", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-table"], 2, 29554)
+def test_bench_two_ranks_prints_per_rank_times_and_verifies(tmp_path):
+    details = str(tmp_path / "details.json")
+    line = _run("bench.py", ["--gpus", "2", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-table", "--details", details], 2, 29554)
+    out = json.load(open(details))  # the full record; the printed line is its summary
+    assert line["verify_ok"] is True and line["n_gpus"] == 2 and line["per_rank"] == out["per_rank"]
     assert out["n_gpus"] == 2 and out["n_ranks_seen"] == 2 and out["verify"]["ok"]
     assert len(out["per_rank"]["ms_per_step_render"]) == 2 and len(out["per_rank"]["gather_ms"]) == 2
 
