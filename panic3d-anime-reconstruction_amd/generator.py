@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import cameras, memo, stylegan2
+from . import cameras, memo, renderer, stylegan2
 from .renderer import ImportanceRenderer
 
 
@@ -126,7 +126,7 @@ class TriPlaneGenerator(torch.nn.Module):
         """Pickling / deep copies (the reference snapshots G): derived tensors and per-call state stay out."""
         state = dict(self.__dict__)
         for k in ("_sign_cache", "_last_planes", "_inject_draws", "_sr_plan", "_ws_memo", "_conv_domain_flag", "_mapping_dicts", "_occ_consts",
-                  "_view_graphs", "_state_list"):
+                  "_view_graphs", "_state_list", "_cond_nets", "_replay_refresh", "_domain_subject"):
             if k in state:
                 state[k] = None
         return state
@@ -199,7 +199,10 @@ class TriPlaneGenerator(torch.nn.Module):
         ans = self._replay_view(ws, cond, ray_origins, ray_directions, res, opts, synthesis_kwargs)
         if ans is None:
             ans = self._synthesis_impl(ws, cond, ray_origins, ray_directions, res, **opts, **synthesis_kwargs)
-            self._domain_end()
+            ent = self.__dict__.pop("_replay_refresh", None)
+            if ent is not None:  # this eager call refreshed the prepared conditioning terms for the entry's tensors
+                ent["epoch"] = self._cond_state()[0]
+            self._domain_end(cond)
         return ans
 
     def _synthesis_impl(self, ws, cond, ray_origins, ray_directions, res, cache_backbone=False, use_cached_backbone=False,
@@ -263,9 +266,25 @@ class TriPlaneGenerator(torch.nn.Module):
     #     of a subject therefore runs eagerly (it refreshes those terms) and its further views replay;
     #   * outputs are CLONES of the capture's buffers: a caller may keep view i while view i + 1 replays.
     # Same launches, same arithmetic, same random stream as the eager call (torch registers the device generator with the capture):
-    # bit-identical images (tests/test_hip_synthesis.py).  Off: memo.set_enabled(False) / P3D_NO_MEMO=1 (no memo layer, no replay),
-    # P3D_VIEW_REPLAY=0, or G.set_view_replay(False).  Not replayed: calls under autograd, with injected draws, latent injections,
-    # cache_backbone / use_cached_backbone, return_more.
+    # bit-identical images (tests/test_hip_synthesis.py, tests/test_hip_view_replay.py).  Off: memo.set_enabled(False) /
+    # P3D_NO_MEMO=1 (no memo layer, no replay), P3D_VIEW_REPLAY=0, or G.set_view_replay(False).  Not replayed: calls under autograd,
+    # with injected draws, latent injections, cache_backbone / use_cached_backbone, return_more.
+    # What keeps a capture from replaying stale launches or stale operands:
+    #   * the key: shapes / dtypes / device of ws, rays and conditioning tensors, the resolution, every call option, the scalar
+    #     rendering_kwargs (the non-scalar ones — avg_camera_pivot — are read by nothing on this path), set_render_exact,
+    #     set_force_sigmoid, cond_mode, and the process-wide switches (stylegan2.switch_state: DEFAULT_CONV_MMA, CONV_IMG,
+    #     TORGB_RIDES, NOISE_POOL / stylegan2.set_noise_pool, ...; renderer.DEFAULT_FAST_COLOR): another value is another entry;
+    #   * a parameter or buffer version that moved (in-place writes, load_state_dict), .to() / .cuda(), clear_memo(),
+    #     set_view_replay(False), a call with the memo layer off: every capture is dropped;
+    #   * a capture keeps alive every cached tensor its launches read: the prepared conditioning terms and the process-wide
+    #     workspace / filter tensors (ops.CAPTURE_KEEP), which their caches may replace while the capture lives;
+    #   * set_conv_mma, set_sr_mma_f16, set_noise_pool: every capture is dropped (they change the launches, and set_conv_mma /
+    #     set_sr_mma_f16 re-derive operands a capture reads: a replay would read freed blocks).  A per-layer `mma_f16` or per-network
+    #     `noise_pool` written by hand is not seen: call clear_memo() after such a write;
+    #   * the prepared conditioning terms (shared by the captures of all call kinds): an entry replays only while the terms hold
+    #     ITS tensors — the same objects at the same versions (`sig`) and no remake of any term since the entry's last eager call or
+    #     capture (`_cond_epoch` of every SynthesisNetwork); otherwise the call runs eagerly, refreshes the terms, and the next call
+    #     of the kind replays.  A term that was REPLACED (`_cond_gen`: it lives at another address now) drops the capture.
     _REPLAY_MAX = 4  # captures kept per generator (each owns the intermediates of a whole view)
 
     def set_view_replay(self, state):
@@ -284,14 +303,28 @@ class TriPlaneGenerator(torch.nn.Module):
     def _apply(self, fn):  # .to() / .cuda() / .float(): every capture holds addresses of the old storage
         self.__dict__["_view_graphs"] = None
         self.__dict__["_state_list"] = None
+        self.__dict__["_cond_nets"] = None
         return super()._apply(fn)
 
+    def _cond_state(self):
+        """((remake epoch, replacement generation) of every SynthesisNetwork's prepared conditioning terms) — what a capture reads
+        besides the inputs it copies in and the parameters' derived operands."""
+        nets = self.__dict__.get("_cond_nets")
+        if nets is None:
+            nets = self.__dict__["_cond_nets"] = [m.__dict__ for m in self.modules() if isinstance(m, stylegan2.SynthesisNetwork)]
+        return tuple([d.get("_cond_epoch", 0) for d in nets]), tuple([d.get("_cond_gen", 0) for d in nets])
+
     def _replay_view(self, ws, cond, ray_origins, ray_directions, res, opts, synthesis_kwargs):
-        """The view from a captured launch sequence, or None (the caller then runs it eagerly)."""
+        """The view from a captured launch sequence, or None (the caller then runs it eagerly; where that call is the entry's refresh,
+        `_replay_refresh` names the entry and synthesis() records the conditioning epoch it left behind)."""
+        self.__dict__["_replay_refresh"] = None
         allowed = self.__dict__.get("_view_replay")
         if allowed is None:
             allowed = os.environ.get("P3D_VIEW_REPLAY", "1") != "0"
-        if not (allowed and memo.enabled() and ws.is_cuda and not torch.is_grad_enabled()) or self._inject_draws is not None \
+        if not memo.enabled():  # calls without the memo layer re-derive the operands a capture reads (and drop the old ones)
+            self.__dict__["_view_graphs"] = None
+            return None
+        if not (allowed and ws.is_cuda and not torch.is_grad_enabled()) or self._inject_draws is not None \
                 or opts["latent_injection"] is not None or opts["cache_backbone"] or opts["use_cached_backbone"] \
                 or _capturing():
             return None
@@ -308,7 +341,8 @@ class TriPlaneGenerator(torch.nn.Module):
             key = (tuple(ws.shape), ws.dtype, ws.device, tuple(ray_origins.shape), ray_origins.dtype, res, opts["stop_level"], opts["triplane_crop"],
                    opts["cull_clouds"], opts["binarize_clouds"], opts["normalize_images"], tuple(sorted(synthesis_kwargs.items())),
                    tuple((k, tuple(v.shape), v.dtype) for k, v in ctens), pver, self.renderer.exact, bool(self.decoder.force_sigmoid),
-                   tuple(sorted((k, v) for k, v in rk.items() if isinstance(v, (int, float, str, bool, type(None))))), self.cond_mode)
+                   tuple(sorted((k, v) for k, v in rk.items() if isinstance(v, (int, float, str, bool, type(None))))), self.cond_mode,
+                   stylegan2.switch_state(), renderer.DEFAULT_FAST_COLOR)
             hash(key)
         except TypeError:  # an option that cannot be compared by value
             return None
@@ -317,20 +351,23 @@ class TriPlaneGenerator(torch.nn.Module):
             graphs = self.__dict__["_view_graphs"] = {"pver": pver, "entries": {}}
         ent = graphs["entries"].get(key)
         sig = tuple((k, id(v), v._version) for k, v in ctens)
-        syn = self.backbone.synthesis
         if ent is None:  # first call of this kind: eager (it also creates every lazily made constant)
             if len(graphs["entries"]) >= self._REPLAY_MAX:
                 graphs["entries"].pop(next(iter(graphs["entries"])))
-            graphs["entries"][key] = {"graph": None, "sig": sig, "cond": [v for _, v in ctens], "failed": False}
+                graphs["evictions"] = graphs.get("evictions", 0) + 1
+            ent = graphs["entries"][key] = {"graph": None, "sig": sig, "cond": [v for _, v in ctens], "failed": False, "epoch": None, "gen": None}
+            self.__dict__["_replay_refresh"] = ent
             return None
         if ent["failed"]:
             return None
-        if ent["sig"] != sig or ent.get("gen") not in (None, syn.__dict__.get("_cond_gen", 0)):
-            # another subject (or conditioning tensors written to): this call runs eagerly and refreshes the prepared terms in place;
-            # a term that had to be REPLACED invalidates the capture
-            if ent.get("gen") not in (None, syn.__dict__.get("_cond_gen", 0)):
-                ent["graph"] = None
-            ent["sig"], ent["cond"], ent["gen"] = sig, [v for _, v in ctens], None
+        epoch, gen = self._cond_state()
+        if ent["graph"] is not None and ent["gen"] != gen:  # a term it reads was REPLACED: the capture reads the old block
+            ent["graph"] = None
+        if ent["sig"] != sig or ent["epoch"] != epoch:
+            # another subject, conditioning tensors written to, or terms remade since for other tensors (another call kind, sample_mixed,
+            # a call under autograd, cache_backbone / latent_injection ...): this call runs eagerly and refreshes the terms in place
+            ent["sig"], ent["cond"] = sig, [v for _, v in ctens]
+            self.__dict__["_replay_refresh"] = ent
             return None
         if ent["graph"] is None:
             try:
@@ -341,7 +378,7 @@ class TriPlaneGenerator(torch.nn.Module):
                 warnings.warn(f"launch replay of TriPlaneGenerator.synthesis disabled for this call signature: {type(e).__name__}: {e}", RuntimeWarning)
                 torch.cuda.synchronize()
                 return None
-            ent["gen"] = syn.__dict__.get("_cond_gen", 0)
+            ent["epoch"], ent["gen"] = self._cond_state()
         ent["ws"].copy_(ws)
         ent["ro"].copy_(ray_origins)
         ent["rd"].copy_(ray_directions)
@@ -350,28 +387,51 @@ class TriPlaneGenerator(torch.nn.Module):
         return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in ent["out"].items()}
 
     def _capture_view(self, ent, ws, cond, ray_origins, ray_directions, res, opts, synthesis_kwargs):
+        from . import ops
         ent["ws"], ent["ro"], ent["rd"] = ws.clone(), ray_origins.clone(), ray_directions.clone()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = self._synthesis_impl(ent["ws"], cond, ent["ro"], ent["rd"], res, **opts, **synthesis_kwargs)
+        ops.CAPTURE_KEEP = []
+        try:
+            with torch.cuda.graph(g):
+                out = self._synthesis_impl(ent["ws"], cond, ent["ro"], ent["rd"], res, **opts, **synthesis_kwargs)
+        finally:
+            shared, ops.CAPTURE_KEEP = ops.CAPTURE_KEEP, None
         ent["graph"], ent["out"] = g, out
-        # what the launches read beyond the inputs and the modules' own state: the prepared conditioning terms (kept alive here)
-        ent["keep"] = list((self.backbone.synthesis.__dict__.get("_cond_cache") or {}).values())
+        # what the launches read beyond the inputs and the modules' own state, kept alive here: the prepared conditioning terms, and
+        # the process-wide cached tensors the capture was handed (the convolution workspace of the capture stream, which a later
+        # capture of a bigger view replaces, and the FIR filters) — this capture's own early launches may use a workspace that its
+        # later ones already replaced
+        self._cond_state()  # (makes the list of conditioned networks)
+        ent["keep"] = [v for d in self.__dict__["_cond_nets"] for v in (d.get("_cond_cache") or {}).values()] \
+            + list({id(t): t for t in shared}.values())
 
-    # ---- the domain of the two-term convolutions, checked once per set of weights -----------------------------------
+    # ---- the domain of the two-term convolutions, checked once per set of weights and once per subject ---------------
     def _domain_begin(self, device):
         if self.__dict__.get("_conv_domain_flag") is None and device.type == "cuda":
             self.watch_conv_domain(device)
 
-    def _domain_end(self):
+    def _domain_end(self, cond=None):
         """The default convolution path (two-term f16 operands) is exact to fp32 class only for |s * x| <= 4094 and SATURATES beyond
-        (stylegan2.DEFAULT_CONV_MMA).  Nothing bounds a real checkpoint's activations (conv_clamp=None, train_eclustrousC.py:554), so
-        the first synthesis after the operands were derived from the weights — construction, load_state_dict,
-        copy_params_and_buffers — reads the generator's flag word back (one 4-byte copy, once per set of weights) and says so."""
+        (stylegan2.DEFAULT_CONV_MMA).  Nothing bounds a real checkpoint's activations (conv_clamp=None, train_eclustrousC.py:554), and
+        |s * x| depends on the weights, the latents and the conditioning images.  So an eager synthesis reads the generator's flag
+        word back (one 4-byte copy) when the operands were derived from new weights — construction, load_state_dict,
+        copy_params_and_buffers — or when its conditioning tensors are not the ones of the last check (a new subject: that call is
+        never a replay), and says so.  Replayed views never read it."""
         flags = self.__dict__.get("_conv_domain_flag")
-        if flags is None or not (flags.dirty or os.environ.get("P3D_CHECK_CONV_DOMAIN")) or _capturing():
+        if flags is None or _capturing():
+            return
+        subject = None
+        if cond is not None:
+            ts = [v for v in cond.values() if torch.is_tensor(v)]
+            subject = (ts, [t._version for t in ts])
+            last = self.__dict__.get("_domain_subject")
+            if last is not None and len(last[0]) == len(ts) and all(a is b for a, b in zip(last[0], ts)) and last[1] == subject[1]:
+                subject = None  # the subject of the last check
+        if not (flags.dirty or subject is not None or os.environ.get("P3D_CHECK_CONV_DOMAIN")):
             return
         flags.dirty = False
+        if subject is not None:
+            self.__dict__["_domain_subject"] = subject
         if self.conv_domain_violated():
             self.__dict__["conv_domain_was_violated"] = True
             import warnings
@@ -388,7 +448,7 @@ class TriPlaneGenerator(torch.nn.Module):
         else:
             self._domain_begin(ws.device)
             planes = self._planes(ws, cond, **synthesis_kwargs)
-            self._domain_end()
+            self._domain_end(cond)
             self._last_planes = planes if reuse else self._last_planes
         return self.renderer.run_model(planes, self.decoder, coordinates, directions, self.rendering_kwargs)
 
@@ -540,7 +600,9 @@ class TriPlaneGenerator(torch.nn.Module):
 
     def set_noise_pool(self, state):
         """noise_mode='random' of THIS generator's backbone and super-resolution: True = one pooled draw per pass, False = the reference's
-        call-for-call torch.randn sequence (seed-compatible with it), None = the process default (stylegan2.NOISE_POOL)."""
+        call-for-call torch.randn sequence (seed-compatible with it), None = the process default (stylegan2.NOISE_POOL).  Drops the
+        captured views (they hold the launches of the other noise path)."""
+        self.__dict__["_view_graphs"] = None
         for net in (self.backbone.synthesis, self.superresolution):
             for m in net.modules():
                 if isinstance(m, stylegan2.SynthesisNetwork):
@@ -555,6 +617,8 @@ class TriPlaneGenerator(torch.nn.Module):
         self.__dict__["_ws_memo"] = None
         self.__dict__["_view_graphs"] = None
         self.__dict__["_state_list"] = None
+        self.__dict__["_cond_nets"] = None
+        self.__dict__["_domain_subject"] = None
         self.__dict__["_mapping_dicts"] = None
         self.__dict__["_occ_consts"] = None
         self._last_planes = None
@@ -579,7 +643,9 @@ class TriPlaneGenerator(torch.nn.Module):
         """How the 3x3 convolutions of the backbone and of the super-resolution feed the matrix cores: "f32" (fp32 operands,
         v_mfma_f32_32x32x2_f32), "x2" (two-term f16 operands: fp32-class results, ~2x faster; domain |s*x| <= 4094, watched by
         watch_conv_domain() / conv_domain_violated()), "f16" (one f16 term: the precision of the reference's fp16 blocks) or None (the
-        package default, stylegan2.DEFAULT_CONV_MMA)."""
+        package default, stylegan2.DEFAULT_CONV_MMA).  Drops the captured views (they hold the other launches and read the
+        operands this re-derives)."""
+        self.__dict__["_view_graphs"] = None
         val = {"f32": False, "x2": "x2", "f16": True, None: None}[mode]
         for m in list(self.backbone.modules()) + list(self.superresolution.modules()):
             if isinstance(m, stylegan2.SynthesisLayer):
@@ -593,7 +659,8 @@ class TriPlaneGenerator(torch.nn.Module):
     def set_sr_mma_f16(self, state=True):
         """Opt-in: run the super-resolution convolutions on f16 MFMA operands (fp32 accumulate, fp32 activations in HBM).
         The reference runs these blocks in fp16 on the GPU (sr_num_fp16_res = 4, superresolution.py:277-280); the default here
-        is exact fp32, which is what its CPU path (the source of the golden fixtures) computes."""
+        is exact fp32, which is what its CPU path (the source of the golden fixtures) computes.  Drops the captured views."""
+        self.__dict__["_view_graphs"] = None
         for m in self.superresolution.modules():
             if isinstance(m, (stylegan2.SynthesisLayer, stylegan2.ToRGBLayer)):
                 m.mma_f16 = bool(state)

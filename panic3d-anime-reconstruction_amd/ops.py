@@ -545,6 +545,17 @@ def _parse_padding(padding):
 
 
 _FIR_CACHE = {}
+# A list while TriPlaneGenerator captures a view into a hipGraph (generator._capture_view), else None: every device tensor that a
+# process-wide cache below hands to the captured launches is appended, and the capture keeps it alive.  A cache may drop its
+# tensor later (a bigger workspace, _FIR_CACHE.clear()), and torch.cuda.graph empties the allocator's cache before every capture:
+# a block that only the cache held can go back to the device while a capture still has its address baked into its launches.
+CAPTURE_KEEP = None
+
+
+def _kept(t):
+    if CAPTURE_KEEP is not None:
+        CAPTURE_KEEP.append(t)
+    return t
 
 
 def prepared_filter(f, device, gain=1.0, flip_filter=False):
@@ -553,7 +564,7 @@ def prepared_filter(f, device, gain=1.0, flip_filter=False):
     key = (id(f), device, float(gain), bool(flip_filter))
     hit = _FIR_CACHE.get(key)
     if memo.enabled() and hit is not None and hit[0]() is f and hit[1] == f._version:
-        return hit[2]
+        return _kept(hit[2])
     ff = f.detach().to(device, torch.float32) * float(gain)
     if not flip_filter:
         ff = ff.flip([0, 1])
@@ -561,7 +572,7 @@ def prepared_filter(f, device, gain=1.0, flip_filter=False):
     if len(_FIR_CACHE) > 256:
         _FIR_CACHE.clear()
     _FIR_CACHE[key] = (weakref.ref(f), f._version, ff)
-    return ff
+    return _kept(ff)
 
 
 def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
@@ -764,7 +775,7 @@ def _conv_scratch(device, nbytes):
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty((int(nbytes * 1.25) + 4096,), dtype=torch.uint8, device=device)
         _CONV_SCRATCH[key] = ws
-    return ws
+    return _kept(ws)
 
 
 class ActImage:

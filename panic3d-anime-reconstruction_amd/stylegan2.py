@@ -145,6 +145,12 @@ def set_noise_pool(state):
     return prev
 
 
+def switch_state():
+    """The process-wide switches above that decide WHICH launches a pass issues, as one tuple (seven global reads, no module walk):
+    part of the key of a captured view (TriPlaneGenerator._replay_view), so a capture never outlives a switch it was made under."""
+    return (DEFAULT_CONV_MMA, DEFAULT_CONV_MMA_1X1, CONV_IMG, IMG_MIN_RES, TORGB_RIDES, NOISE_POOL, STYLE_MEMO)
+
+
 def _takes_image(layer, res):
     """A plain 3x3 layer that can stage its input from an activation image: two-term operands, 16-channel K chunks, a map of at
     least IMG_MIN_RES columns (the wide-tile kernel)."""
@@ -596,6 +602,9 @@ class SynthesisNetwork(_CacheFree):
         # Round 6: a term prepared for OTHER conditioning tensors of the same shape (the next subject) is written INTO the tensor the
         # previous subject's term lived in: the prepared terms keep their addresses, which a captured view (TriPlaneGenerator's
         # launch replay) has baked into its launches.  A term that cannot be updated in place is replaced, and `_cond_gen` says so.
+        # `_cond_epoch` moves on EVERY remake, in place or not: the terms' values changed, and a capture made for other tensors must
+        # not replay until an eager call of its own has refreshed them (the captures of all call kinds share these terms).
+        self.__dict__["_cond_epoch"] = self.__dict__.get("_cond_epoch", 0) + 1
         if hit is not None and hit[1].shape == val.shape and hit[1].dtype == val.dtype and hit[1].device == val.device \
                 and not torch.is_grad_enabled():
             hit[1].copy_(val)
@@ -610,6 +619,7 @@ class SynthesisNetwork(_CacheFree):
         resized copies: a long-running server calls this between subjects, or when it is done; G.to(device) does it too)."""
         if self.__dict__.pop("_cond_cache", None) is not None:
             self.__dict__["_cond_gen"] = self.__dict__.get("_cond_gen", 0) + 1
+            self.__dict__["_cond_epoch"] = self.__dict__.get("_cond_epoch", 0) + 1
 
     def _apply(self, fn):  # .to() / .cuda() / .float(): prepared terms live on the old device
         self.clear_cond_cache()
