@@ -103,6 +103,18 @@ SIGNATURES = {
     "p3d_abi_version": (_I, []),
 }
 
+# symbol -> (restype, argtypes); every function include/p3d_render_grad.h declares (the backward passes).  A table of its own:
+# SIGNATURES mirrors include/panic3d_hip.h exactly.
+GRAD_SIGNATURES = {
+    "p3d_render_backward_workspace_bytes": (_Z, [_I, _L, _I, _I]),
+    "p3d_render_backward_f32": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P, C.POINTER(Opts), _P, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _Z, _P]),
+    "p3d_triplane_decode_backward_workspace_bytes": (_Z, [_I, _L]),
+    "p3d_triplane_decode_backward_f32": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _P, _P, C.POINTER(Opts), _P, _P, _P, _P, _P, _P, _P,
+                                              _P, _Z, _P]),
+}
+P3D_GRAD_STATS_BYTES = 256  # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
+
 _LIB = None
 
 
@@ -120,7 +132,7 @@ def lib():
                 print(f"panic3d_amd: {SO} does not match csrc/ (source hash): rebuilding", file=sys.stderr)
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

@@ -4,7 +4,9 @@ checkpoint's init kwargs and copy the parameters by name), with the backbone on 
 (stylegan2.py), the volumetric renderer on the fused HIP kernel (renderer.py) and the super-resolution blocks on the same
 modulated-conv kernel.
 
-Inference only.  Not mirrored: `sample` (broken in the reference, triplane.py:254-271).  The `paste_front`
+The backbone and the super-resolution are inference-only (`image` carries no gradient).  With grad enabled, `image_raw`,
+`image_depth`, `image_weights` and `image_xyz` carry gradients through the renderer's HIP backward to the decoder parameters
+(and to the planes when a caller renders planes that require grad; renderer.py).  Not mirrored: `sample` (broken in the reference, triplane.py:254-271).  The `paste_front`
 post-process (triplane.py:555-691) lives in paste.py.
 """
 import os

@@ -15,7 +15,7 @@ from . import _lib, memo
 from ._lib import Opts, Dumps
 
 __all__ = ["make_opts", "prescale_mlp", "planes_to_nhwc", "triplane_decode", "render", "sample_stratified", "composite",
-           "importance", "unify_perm"]
+           "importance", "unify_perm", "render_backward", "triplane_decode_backward"]
 
 
 # torch.cuda.current_stream() builds a Stream object through three layers of Python (~7 us) and torch.cuda.current_device() goes
@@ -351,12 +351,13 @@ def render(planes_nhwc, rays_o, rays_d, jitter, u, mlp, opts, ray_tile_w=0, dump
     if dumps:
         NR, S = N * R, Sc + Sf
         f32 = dict(dtype=torch.float32, device=dev)
-        d = dict(depths_coarse=torch.empty((NR, Sc), **f32), sigma_coarse=torch.empty((NR, Sc), **f32),
-                 weights_coarse=torch.empty((NR, Sc - 1), **f32), depths_fine=torch.empty((NR, Sf), **f32),
-                 inds=torch.empty((NR, Sf), dtype=torch.int32, device=dev), depths_sorted=torch.empty((NR, S), **f32),
-                 sigma_sorted=torch.empty((NR, S), **f32), depth_unclamped=torch.empty((NR,), **f32),
-                 tminmax=torch.empty((2,), **f32))
-        dm = Dumps(*[_p(d[k]) for k in DUMP_KEYS])
+        shapes = dict(depths_coarse=(NR, Sc), sigma_coarse=(NR, Sc), weights_coarse=(NR, Sc - 1), depths_fine=(NR, Sf), inds=(NR, Sf),
+                      depths_sorted=(NR, S), sigma_sorted=(NR, S), depth_unclamped=(NR,), tminmax=(2,))
+        keys = DUMP_KEYS if dumps is True else tuple(dumps)  # a collection of names: only those stages are dumped
+        if any(k not in shapes for k in keys):
+            raise RuntimeError(f"render: unknown dump names {sorted(set(keys) - set(shapes))}")
+        d = {k: torch.empty(shapes[k], dtype=torch.int32, device=dev) if k == "inds" else torch.empty(shapes[k], **f32) for k in keys}
+        dm = Dumps(*[_p(d.get(k)) for k in DUMP_KEYS])
     rs_t = re_t = None
     if ray_limits is not None and (opts.flags & _lib.P3D_FLAG_DISPARITY):
         raise NotImplementedError("disparity_space_sampling with per-ray limits")
@@ -396,6 +397,87 @@ def render(planes_nhwc, rays_o, rays_d, jitter, u, mlp, opts, ray_tile_w=0, dump
     if weights_only:  # (feat / xyz may have been left unwritten)
         return None, depth, wsum, None
     return (feat, depth, wsum, xyz, d) if dumps else (feat, depth, wsum, xyz)
+
+
+def _grad_out(t, name, shape):
+    if t is None:
+        return None
+    t = _chk(t, name)
+    if t.numel() != int(np.prod(shape)):
+        raise RuntimeError(f"{name} must hold {int(np.prod(shape))} values ({list(shape)})")
+    return t
+
+
+def _grad_buffers(planes_nhwc, dev, want_planes=True):
+    dplanes = torch.zeros(planes_nhwc.shape, dtype=torch.float32, device=dev) if want_planes else None
+    dmlp = (torch.empty((64, 32), dtype=torch.float32, device=dev), torch.empty((64,), dtype=torch.float32, device=dev),
+            torch.empty((33, 64), dtype=torch.float32, device=dev), torch.empty((33,), dtype=torch.float32, device=dev))
+    return dplanes, dmlp
+
+
+def render_backward(planes_nhwc, rays_o, rays_d, depths_sorted, mlp, opts, grads, per_view_clamp=False, stats=None, want_planes=True):
+    """Backward of render() (include/p3d_render_grad.h p3d_render_backward_f32) at the forward's merged depths
+    (render(..., dumps=("depths_sorted",))).  grads = (g_feat [N,R,32], g_depth [N,R,1], g_wsum [N,R,1], g_xyz [N,R,3]), any
+    None.  Returns (d_planes_nhwc shaped like planes_nhwc, (d_w0, d_b0, d_w1, d_b1)) — gradients of the pre-scaled decoder
+    tensors.  opts: the forward's (per_view_clamp as passed to render).  stats: a dict receives the number of samples that ran
+    the MLP backward (synchronises).  want_planes=False: decoder gradients only (d_planes_nhwc is None, no scatter)."""
+    if per_view_clamp:
+        opts = _with_flag(opts, _lib.P3D_FLAG_PER_VIEW_CLAMP)
+    planes_nhwc = _chk(planes_nhwc, "planes_nhwc")
+    rays_o, rays_d = _chk(rays_o, "ray_origins"), _chk(rays_d, "ray_directions")
+    N, three, H, W, Cc = planes_nhwc.shape
+    if N == 1 and rays_o.dim() == 3 and rays_o.shape[0] > 1:
+        N, opts = rays_o.shape[0], _with_flag(opts, _lib.P3D_FLAG_SHARED_PLANES)
+    if three != 3 or Cc != 32 or rays_o.dim() != 3 or rays_o.shape[0] != N or rays_o.shape[2] != 3 or rays_d.shape != rays_o.shape:
+        raise RuntimeError("planes_nhwc must be [N,3,H,W,32] (or [1,...] shared by all views); ray_origins / ray_directions [N,R,3]")
+    R, S = rays_o.shape[1], opts.Sc + opts.Sf
+    depths_sorted = _grad_out(depths_sorted, "depths_sorted", (N * R, S))
+    if depths_sorted is None:
+        raise RuntimeError("render_backward needs the forward's depths_sorted dump")
+    g_feat, g_depth, g_wsum, g_xyz = (_grad_out(g, n, sh) for g, n, sh in zip(
+        grads, ("grad feat", "grad depth", "grad wsum", "grad xyz"), ((N, R, 32), (N, R, 1), (N, R, 1), (N, R, 3))))
+    w0, b0, w1, b1 = _chk_mlp(mlp)
+    dev = rays_o.device
+    dplanes, dmlp = _grad_buffers(planes_nhwc, dev, want_planes)
+    L = _lib.lib()
+    wsb = L.p3d_render_backward_workspace_bytes(N, R, opts.Sc, opts.Sf)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        rc = L.p3d_render_backward_f32(_p(planes_nhwc), N, H, W, _p(rays_o), _p(rays_d), R, _p(depths_sorted), _p(w0), _p(b0), _p(w1),
+                                       _p(b1), C.byref(opts), _p(g_feat), _p(g_depth), _p(g_wsum), _p(g_xyz), _p(dplanes),
+                                       *(_p(t) for t in dmlp), _p(ws), wsb, _stream())
+    _lib.check(rc, "p3d_render_backward_f32")
+    if stats is not None:
+        stats.update(executed_samples=int(ws[:8].view(torch.int64).item()), samples=N * R * S)
+    return dplanes, dmlp
+
+
+def triplane_decode_backward(planes_nhwc, coords, mlp, opts, g_sigma, g_rgb, stats=None, want_planes=True):
+    """Backward of triplane_decode() (p3d_triplane_decode_backward_f32): g_sigma [N,M,1], g_rgb [N,M,32] (either None) ->
+    (d_planes_nhwc, (d_w0, d_b0, d_w1, d_b1)).  Masks of opts.flags zero the density gradient where they overwrite it."""
+    planes_nhwc = _chk(planes_nhwc, "planes_nhwc")
+    coords = _chk(coords, "coords")
+    N, three, H, W, Cc = planes_nhwc.shape
+    if N == 1 and coords.dim() == 3 and coords.shape[0] > 1:
+        N, opts = coords.shape[0], _with_flag(opts, _lib.P3D_FLAG_SHARED_PLANES)
+    if three != 3 or Cc != 32 or coords.dim() != 3 or coords.shape[0] != N or coords.shape[2] != 3:
+        raise RuntimeError("planes_nhwc must be [N,3,H,W,32] (or [1,...] shared) and coords [N,M,3]")
+    M = coords.shape[1]
+    g_sigma = _grad_out(g_sigma, "grad sigma", (N, M, 1))
+    g_rgb = _grad_out(g_rgb, "grad rgb", (N, M, 32))
+    w0, b0, w1, b1 = _chk_mlp(mlp)
+    dev = coords.device
+    dplanes, dmlp = _grad_buffers(planes_nhwc, dev, want_planes)
+    L = _lib.lib()
+    wsb = L.p3d_triplane_decode_backward_workspace_bytes(N, M)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        rc = L.p3d_triplane_decode_backward_f32(_p(planes_nhwc), N, H, W, _p(coords), M, _p(w0), _p(b0), _p(w1), _p(b1), C.byref(opts),
+                                                _p(g_sigma), _p(g_rgb), _p(dplanes), *(_p(t) for t in dmlp), _p(ws), wsb, _stream())
+    _lib.check(rc, "p3d_triplane_decode_backward_f32")
+    if stats is not None:
+        stats.update(executed_samples=int(ws[:8].view(torch.int64).item()), samples=N * M)
+    return dplanes, dmlp
 
 
 def sample_stratified(ray_start, ray_end, S, jitter):

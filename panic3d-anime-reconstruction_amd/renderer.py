@@ -5,6 +5,12 @@ training/volumetric_rendering/renderer.py:156-387 (ImportanceRenderer) so that
 training/triplane.py:209 (`self.renderer(planes, self.decoder, ray_origins, ray_directions, rendering_kwargs, ...)`)
 and :292 (`self.renderer.run_model(...)`) keep working when the class is swapped in.
 
+Gradients: with autograd recording and the planes or a decoder parameter requiring grad, forward() and run_model() return
+outputs with a grad_fn (the fused forward with its depths_sorted dump, bit-identical outputs, and the HIP backward of
+include/p3d_render_grad.h); the planes and the raw net.*.weight / bias receive gradients.  Rays, ray limits and depths get none
+(requiring grad on a ray raises NotImplementedError).  return_dumps / weights_only calls and the staged density_noise path stay
+inference-only.
+
 Differences that are deliberate:
   * the two random draws (renderer.py:324 `torch.rand_like`, :371 `torch.rand`) are made on the device with the same
     call order and shapes, or injected via `jitter=` / `u=` (parity tests, CPU-generated draws);
@@ -29,9 +35,35 @@ from . import memo, ops
 DEFAULT_FAST_COLOR = os.environ.get("P3D_EXACT", "0") != "1"
 
 
-def decoder_params(decoder):
-    """(w0, b0, w1, b1) pre-scaled exactly like FullyConnectedLayer.forward (networks_stylegan2.py:121-127)."""
+def _decoder_tensors(decoder):
     l0, l2 = decoder.net[0], decoder.net[2]
+    return [t for t in (l0.weight, l0.bias, l2.weight, l2.bias) if t is not None]
+
+
+def grad_wanted(planes, decoder):
+    """True when autograd is recording and the planes or a decoder parameter require grad: the renderer then takes its
+    differentiable path (a torch.autograd.Function over the fused kernel and its HIP backward)."""
+    if not torch.is_grad_enabled() or torch.is_inference_mode_enabled():
+        return False
+    return bool((planes is not None and planes.requires_grad) or any(t.requires_grad for t in _decoder_tensors(decoder)))
+
+
+def decoder_params(decoder, live=None):
+    """(w0, b0, w1, b1) pre-scaled exactly like FullyConnectedLayer.forward (networks_stylegan2.py:121-127).
+    live (default: autograd is recording and a parameter requires grad): the same two multiplications as torch ops on the
+    parameters themselves, so that the raw net.*.weight / bias receive their lr_multiplier-scaled gradients; same bits."""
+    l0, l2 = decoder.net[0], decoder.net[2]
+    if live is None:
+        live = grad_wanted(None, decoder)
+    if live:
+        out = []
+        for layer in (l0, l2):
+            w = layer.weight.float() * layer.weight_gain
+            b = layer.bias.float()
+            if layer.bias_gain != 1:
+                b = b * layer.bias_gain
+            out += [w, b]
+        return tuple(out)
     if hasattr(l0, "_scaled") and hasattr(l2, "_scaled"):
         # this package's FullyConnectedLayer keeps `w * weight_gain`, `b * bias_gain` per parameter version (the same two
         # multiplications, so the same bits): two launches and ~20 us of host time less per render
@@ -39,6 +71,68 @@ def decoder_params(decoder):
         return w0, b0, w1, b1
     return ops.prescale_mlp(l0.weight, l0.bias, l2.weight, l2.bias, l0.weight_gain, l0.bias_gain, l2.weight_gain,
                             l2.bias_gain)
+
+
+def _nchw_grad(dplanes_nhwc, shape):
+    """NHWC plane gradient [n,3,H,W,32] -> the caller's NCHW [N,3,32,H,W].  Planes expanded from one subject (stride 0 along N,
+    P3D_FLAG_SHARED_PLANES) get the whole sum in slice 0 and zeros elsewhere: expand's backward sums them onto the base exactly."""
+    g = dplanes_nhwc.permute(0, 1, 4, 2, 3)
+    if g.shape[0] != shape[0]:
+        full = torch.zeros(shape, dtype=g.dtype, device=g.device)
+        full[:1] = g
+        return full
+    return g.contiguous()
+
+
+class _RenderFunction(torch.autograd.Function):
+    """The fused forward (ops.render with the depths_sorted dump) and p3d_render_backward_f32.  Inputs that receive gradients:
+    planes (NCHW) and the four pre-scaled decoder tensors; everything else rides in `call`."""
+
+    @staticmethod
+    def forward(ctx, planes, w0, b0, w1, b1, call):
+        nhwc = call["nhwc"]
+        key = "depths_sorted" if call["opts"].Sf > 0 else "depths_coarse"  # single pass: the merged depths are the coarse ones
+        feat, depth, wsum, xyz, d = ops.render(nhwc, call["rays_o"], call["rays_d"], call["jitter"], call["u"], (w0, b0, w1, b1),
+                                               call["opts"], ray_tile_w=call["ray_tile_w"], dumps=(key,),
+                                               per_view_clamp=call["per_view_clamp"], ray_limits=call["limits"])
+        ctx.call = dict(nhwc=nhwc, rays_o=call["rays_o"], rays_d=call["rays_d"], opts=call["opts"], per_view_clamp=call["per_view_clamp"],
+                        depths=d[key], mlp=(w0, b0, w1, b1))
+        ctx.planes_shape = tuple(planes.shape)
+        return feat, depth, wsum, xyz
+
+    @staticmethod
+    def backward(ctx, g_feat, g_depth, g_wsum, g_xyz):
+        c = ctx.call
+        dpl, dmlp = ops.render_backward(c["nhwc"], c["rays_o"], c["rays_d"], c["depths"], c["mlp"], c["opts"], (g_feat, g_depth, g_wsum, g_xyz),
+                                        per_view_clamp=c["per_view_clamp"], want_planes=ctx.needs_input_grad[0])
+        dplanes = _nchw_grad(dpl, ctx.planes_shape) if ctx.needs_input_grad[0] else None
+        return (dplanes,) + tuple(g if need else None for g, need in zip(dmlp, ctx.needs_input_grad[1:5])) + (None,)
+
+
+class _DecodeFunction(torch.autograd.Function):
+    """ops.triplane_decode and p3d_triplane_decode_backward_f32 (run_model)."""
+
+    @staticmethod
+    def forward(ctx, planes, w0, b0, w1, b1, call):
+        sigma, rgb = ops.triplane_decode(call["nhwc"], call["coords"], (w0, b0, w1, b1), call["opts"])
+        ctx.call = dict(call, mlp=(w0, b0, w1, b1))
+        ctx.planes_shape = tuple(planes.shape)
+        return sigma, rgb
+
+    @staticmethod
+    def backward(ctx, g_sigma, g_rgb):
+        c = ctx.call
+        dpl, dmlp = ops.triplane_decode_backward(c["nhwc"], c["coords"], c["mlp"], c["opts"], g_sigma, g_rgb,
+                                                 want_planes=ctx.needs_input_grad[0])
+        dplanes = _nchw_grad(dpl, ctx.planes_shape) if ctx.needs_input_grad[0] else None
+        return (dplanes,) + tuple(g if need else None for g, need in zip(dmlp, ctx.needs_input_grad[1:5])) + (None,)
+
+
+def _no_ray_grads(**tensors):
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise NotImplementedError(f"ImportanceRenderer: gradients with respect to {name} are not implemented (only planes and "
+                                      "decoder parameters receive gradients)")
 
 
 class ImportanceRenderer(torch.nn.Module):
@@ -112,6 +206,14 @@ class ImportanceRenderer(torch.nn.Module):
         if ray_tile_w is None:  # square images are the reference's only use (training/triplane.py:222-226)
             side = int(round(R ** 0.5))
             ray_tile_w = side if side * side == R else 0
+        if not return_dumps and not weights_only and grad_wanted(planes, decoder):
+            # differentiable path: the same kernel family with the depths_sorted dump (the every-sample kernel, same bits)
+            _no_ray_grads(ray_origins=ray_origins, ray_directions=ray_directions,
+                          ray_start=None if limits is None else limits[0], ray_end=None if limits is None else limits[1])
+            w0, b0, w1, b1 = decoder_params(decoder, live=True)
+            call = dict(nhwc=self._nhwc(planes), rays_o=ray_origins.float(), rays_d=ray_directions.float(), jitter=jitter, u=u,
+                        opts=opts, ray_tile_w=ray_tile_w, per_view_clamp=per_view_clamp, limits=limits)
+            return _RenderFunction.apply(planes, w0, b0, w1, b1, call)
         out = ops.render(self._nhwc(planes), ray_origins.float(), ray_directions.float(), jitter, u,
                          decoder_params(decoder), opts, ray_tile_w=ray_tile_w, dumps=return_dumps, per_view_clamp=per_view_clamp,
                          ray_limits=limits, weights_only=weights_only)
@@ -128,6 +230,7 @@ class ImportanceRenderer(torch.nn.Module):
         (renderer.py:276-277, `sigma += randn_like(sigma) * density_noise` inside run_model, i.e. BEFORE the crop / cull masks), which
         needs a value per decoded sample that the final pass of the fused kernel, re-decoding the coarse samples, would have to see
         twice.  Without noise it computes what forward() computes (tested), far slower.  Fixed ray limits, linear depth spacing.
+        No gradients: its stages are inference kernels (the differentiable path is forward() without density_noise).
         density_noise_draws: (noise of the coarse pass [N,R*Sc,1], of the fine pass [N,R*Sf,1]) — parity tests; default: torch.randn
         on the device, drawn in the reference's order (jitter, coarse noise, u, fine noise)."""
         ro = dict(rendering_options)
@@ -189,7 +292,13 @@ class ImportanceRenderer(torch.nn.Module):
         if dn > 0:  # renderer.py:276-277: `out['sigma'] += torch.randn_like(out['sigma']) * options['density_noise']` after the decode
             options = {k: v for k, v in options.items() if k != "density_noise"}
         opts = self._opts(options, decoder)
-        sigma, rgb = ops.triplane_decode(self._nhwc(planes), sample_coordinates.float(), decoder_params(decoder), opts)
+        if grad_wanted(planes, decoder):
+            _no_ray_grads(sample_coordinates=sample_coordinates)
+            w0, b0, w1, b1 = decoder_params(decoder, live=True)
+            call = dict(nhwc=self._nhwc(planes), coords=sample_coordinates.float().contiguous(), opts=opts)
+            sigma, rgb = _DecodeFunction.apply(planes, w0, b0, w1, b1, call)
+        else:
+            sigma, rgb = ops.triplane_decode(self._nhwc(planes), sample_coordinates.float(), decoder_params(decoder), opts)
         if dn > 0:
             sigma = sigma + torch.randn_like(sigma) * dn
         return {"rgb": rgb, "sigma": sigma, "xyz": sample_coordinates}
