@@ -41,8 +41,8 @@ extern "C" {
 #define P3D_FLAG_WHITE_BACK 16   /* rendering_options.white_back (ray_marcher.py:52-53) */
 #define P3D_FLAG_NO_EARLY_OUT 32 /* p3d_render_f32: disable the exact early-outs (decode every sample; measurement / tests) */
 #define P3D_FLAG_NO_PAIR 256 /* p3d_render_f32: never use a small-launch kernel (8 rays x 4 samples / 16 rays x 2 samples per wave); tests */
-#define P3D_FLAG_PAIR16 16384 /* p3d_render_f32: small launches take the 16 rays x 2 samples kernel (k_render_pair) ... */
-#define P3D_FLAG_QUAD8 32768  /* ... / the 8 rays x 4 samples kernel (k_render_quad), whatever the size heuristic says (default: quad for
+#define P3D_FLAG_PAIR16 16384 /* p3d_render_f32: small launches take the 16 rays x 2 samples kernel (k_render_slots<2, ...>) ... */
+#define P3D_FLAG_QUAD8 32768  /* ... / the 8 rays x 4 samples kernel (k_render_slots<4, ...>), whatever the size heuristic says (default: quad for
                                  launches of <= 8192 rays and for the tolerance mode at 96+96 samples, pair otherwise); tests, A/B timing */
 #define P3D_FLAG_SKIP_CROPPED 128 /* p3d_grid_density_f32 with out_cropmask: points whose crop mask fires are not decoded and get
                                      out_sigma = -1000 (get_eg3d_volume overwrites their density anyway, eg3d_metrics3d.py:155-159) */

@@ -6,7 +6,8 @@
 //   k_render           ImportanceRenderer.forward fused per wavefront: 32 rays per wave (lane pair = ray x channel half);
 //                      coarse density pass -> weights -> importance resampling -> merge -> final decode + compositing,
 //                      all per-ray state in registers / LDS; no intermediate tensor ever reaches HBM.
-//   k_render_pair      the same algorithm for small launches: 16 rays x 2 samples per wave (bit-identical results).
+//   k_render_slots     the same algorithm for small launches: 32 / SLOTS rays x SLOTS samples per wave, SLOTS = 2 or 4
+//                      (bit-identical results).
 //   k_render_finish    the one cross-ray dependency: depth clamp to the global [min t, max t] (ray_marcher.py:49-50).
 //   k_sigma2density    get_eg3d_volume's activation + crop / cull masks in one pass.
 //   k_stratified / k_composite / k_importance / k_unify_perm   operator-level stand-alone stages (one thread per ray).
@@ -18,6 +19,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "p3d_decode.hpp"
 
@@ -34,7 +36,7 @@
 #define P3D_QUAD_EXACT 1
 #endif
 #ifndef P3D_QUAD_PAIR
-#define P3D_QUAD_PAIR 1     // ... and in the small-launch kernel k_render_pair
+#define P3D_QUAD_PAIR 1     // ... and in the small-launch kernel k_render_slots
 #endif
 #ifndef P3D_RENDER_OCC
 #define P3D_RENDER_OCC 2    // waves per SIMD the register allocation of k_render is held to (launch_bounds) and the host packs for
@@ -369,7 +371,7 @@ P3D_DEV void p3d_sort_network(float (&a)[NR]) {
 }
 
 // insertion sort of rows [0, n) of a per-wave LDS column (generic / rare path)
-template <int RS = 32>  // RS: floats per LDS row (32 rays per wave; 8 in k_render_quad)
+template <int RS = 32>  // RS: floats per LDS row (the rays of a wave: 32 in k_render, 32 / SLOTS in k_render_slots)
 P3D_DEV void p3d_lds_insertion_sort(float* A, int n, int j) {
     for (int i = 1; i < n; ++i) {
         float key = A[i * RS + j];
@@ -384,36 +386,13 @@ P3D_DEV void p3d_lds_insertion_sort(float* A, int n, int j) {
     }
 }
 
-// one inverse-CDF draw: renderer.py:371-386.  cdf rows [0, Ns], coarse depths tc rows [0, Sc)
-template <int RS = 32>
-P3D_DEV float p3d_inverse_cdf(const float* cdfA, const float* tcA, int Ns, int j, float ui, int& k_out) {
+// B independent inverse-CDF draws: renderer.py:371-386.  cdf rows [0, Ns] of the LDS column j (RS floats per row); the coarse
+// depths, rows [0, Sc), behind a functor tc(index): an LDS column, or in k_render's TCG instantiations recomputed from the jitter
+// tensor.  The B LDS reads of every search step are in flight together (one draw is a chain of 8 dependent LDS round trips; 48 of
+// them back to back were ~9 % of k_render).
+template <int B, int RS, typename TCF>
+P3D_DEV void p3d_inverse_cdf(const float* cdfA, TCF tc, int Ns, int j, const float (&ui)[B], float (&out)[B], int (&k_out)[B]) {
     // k = #{q in 0..Ns : cdf[q] <= u}  (searchsorted right=True): branchless binary search on the non-decreasing cdf
-    const int n = Ns + 1;
-    int pos = 0;
-#pragma unroll
-    for (int step = 128; step >= 1; step >>= 1) {
-        int np = pos + step;
-        if (step <= n) {  // wave-uniform
-            bool ok = (np <= n) && (cdfA[((np <= n) ? np - 1 : 0) * RS + j] <= ui);
-            pos = ok ? np : pos;
-        }
-    }
-    int k = pos;
-    int below = k - 1 > 0 ? k - 1 : 0;
-    int above = k < Ns ? k : Ns;
-    float cb = cdfA[below * RS + j], ca = cdfA[above * RS + j];
-    float den = ca - cb;
-    if (den < 1e-5f) den = 1.0f;
-    float bb = 0.5f * (tcA[below * RS + j] + tcA[(below + 1) * RS + j]);
-    float ba = 0.5f * (tcA[above * RS + j] + tcA[(above + 1) * RS + j]);
-    k_out = k;
-    return bb + ((ui - cb) / den) * (ba - bb);
-}
-
-// B independent draws at once: the same arithmetic as p3d_inverse_cdf, with the B LDS reads of every search step in flight
-// together (one draw is a chain of 8 dependent LDS round trips; 48 of them back to back were ~9 % of k_render).
-template <int B, int RS = 32>
-P3D_DEV void p3d_inverse_cdf_batch(const float* cdfA, const float* tcA, int Ns, int j, const float (&ui)[B], float (&out)[B], int (&k_out)[B]) {
     const int n = Ns + 1;
     int pos[B];
 #pragma unroll
@@ -434,8 +413,8 @@ P3D_DEV void p3d_inverse_cdf_batch(const float* cdfA, const float* tcA, int Ns, 
         const int k = pos[q], below = k - 1 > 0 ? k - 1 : 0, above = k < Ns ? k : Ns;
         k_out[q] = k;
         cb[q] = cdfA[below * RS + j]; ca[q] = cdfA[above * RS + j];
-        t0[q] = tcA[below * RS + j]; t1[q] = tcA[(below + 1) * RS + j];
-        t2[q] = tcA[above * RS + j]; t3[q] = tcA[(above + 1) * RS + j];
+        t0[q] = tc(below); t1[q] = tc(below + 1);
+        t2[q] = tc(above); t3[q] = tc(above + 1);
     }
 #pragma unroll
     for (int q = 0; q < B; ++q) {
@@ -446,43 +425,6 @@ P3D_DEV void p3d_inverse_cdf_batch(const float* cdfA, const float* tcA, int Ns, 
         // the result exists HERE: without this the optimiser sinks the lerp (and keeps its six LDS operands alive) down to the
         // first use — the sorting network behind the last batch: 6 x Sf live values, 82-169 spilled VGPRs in the NF = 48 / 96 kernels
         asm volatile("" : "+v"(out[q]));
-    }
-}
-
-// The same with the coarse depths behind a functor tc(index) instead of an LDS column (k_render's TCG instantiations recompute
-// them from the jitter tensor).  Identical arithmetic.
-template <int B, typename TCF>
-P3D_DEV void p3d_inverse_cdf_batch_f(const float* cdfA, TCF tc, int Ns, int j, const float (&ui)[B], float (&out)[B], int (&k_out)[B]) {
-    const int n = Ns + 1;
-    int pos[B];
-#pragma unroll
-    for (int q = 0; q < B; ++q) pos[q] = 0;
-#pragma unroll
-    for (int step = 128; step >= 1; step >>= 1) {
-        if (step <= n) {  // wave-uniform
-            float c[B];
-#pragma unroll
-            for (int q = 0; q < B; ++q) c[q] = cdfA[((pos[q] + step <= n) ? pos[q] + step - 1 : 0) * 32 + j];
-#pragma unroll
-            for (int q = 0; q < B; ++q) pos[q] = ((pos[q] + step <= n) && (c[q] <= ui[q])) ? pos[q] + step : pos[q];
-        }
-    }
-    float cb[B], ca[B], t0[B], t1[B], t2[B], t3[B];
-#pragma unroll
-    for (int q = 0; q < B; ++q) {
-        const int k = pos[q], below = k - 1 > 0 ? k - 1 : 0, above = k < Ns ? k : Ns;
-        k_out[q] = k;
-        cb[q] = cdfA[below * 32 + j]; ca[q] = cdfA[above * 32 + j];
-        t0[q] = tc(below); t1[q] = tc(below + 1);
-        t2[q] = tc(above); t3[q] = tc(above + 1);
-    }
-#pragma unroll
-    for (int q = 0; q < B; ++q) {
-        float den = ca[q] - cb[q];
-        if (den < 1e-5f) den = 1.0f;
-        const float bb = 0.5f * (t0[q] + t1[q]), ba = 0.5f * (t2[q] + t3[q]);
-        out[q] = bb + ((ui[q] - cb[q]) / den) * (ba - bb);
-        asm volatile("" : "+v"(out[q]));  // (see p3d_inverse_cdf_batch)
     }
 }
 
@@ -599,6 +541,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
     float* tcA = wl;             // [Sc]            coarse depths (TCG: no such rows)
     float* wcA = TCG ? wl : tcA + Sc * 32;  // [max(Sc,Sf)]    coarse weights -> pdf/cdf (row 0 = cdf[0]) -> (NF path) sorted fine depths
     float* tfA = (NF > 0) ? wcA : wcA + Sc * 32;  // [Sf] sorted fine depths
+    auto tc_lds = [&](int i) { return tcA[i * 32 + j]; };
     uint32_t* mkA = (uint32_t*)(wl + (size_t)(p.lds_rows - ((Sc + 31) >> 5)) * 32);  // [ceil(Sc/32)] known-masked bits of the coarse samples
     const int nmw = (S + 31) >> 5;                         // words of a bit row over the merged list
     uint32_t* knA = TCG ? (uint32_t*)(wl + (size_t)(Sc > Sf ? Sc : Sf) * 32) : mkA - (size_t)2 * nmw * 32;  // [ceil(S/32)] merged sample q: sigma = -1000 known without a decode
@@ -801,8 +744,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
                     int kb[DB];
 #pragma unroll
                     for (int q = 0; q < DB; ++q) ub[q] = tf[i0 + q];
-                    if constexpr (TCG) p3d_inverse_cdf_batch_f<DB>(wcA, tc_raw, Ns, j, ub, vb, kb);
-                    else p3d_inverse_cdf_batch<DB>(wcA, tcA, Ns, j, ub, vb, kb);
+                    if constexpr (TCG) p3d_inverse_cdf<DB, 32>(wcA, tc_raw, Ns, j, ub, vb, kb);
+                    else p3d_inverse_cdf<DB, 32>(wcA, tc_lds, Ns, j, ub, vb, kb);
 #pragma unroll
                     for (int q = 0; q < DB; ++q) {
                         tf[i0 + q] = (i0 + q < Sf) ? vb[q] : __builtin_inff();
@@ -836,7 +779,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
                     const int iq = i0 + q < Sf ? i0 + q : Sf - 1;
                     ub[q] = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, iq) : uu[iq];
                 }
-                p3d_inverse_cdf_batch<DB>(wcA, tcA, Ns, j, ub, vb, kb);
+                p3d_inverse_cdf<DB, 32>(wcA, tc_lds, Ns, j, ub, vb, kb);
 #pragma unroll
                 for (int q = 0; q < DB; ++q) {
                     if (i0 + q < Sf) {
@@ -1138,371 +1081,79 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
     }
 }
 
-// =====================================================================================================================
-// k_render_pair: the same algorithm for SMALL launches (fewer 32-ray tiles than the chip has SIMDs, e.g. the pipeline's single
-// 128^2-ray views: 512 tiles on 1024 SIMDs, each wave alone on its SIMD and ALU-bound at ~4.7 us per decode step).  A wave owns
-// 16 rays and decodes TWO consecutive samples of every ray per step: lane j = ray (j & 15) x sample slot (j >> 4) x channel half,
-// so a launch makes twice as many waves, each with half as many decode steps.  Everything per ray (depth rows in LDS, marcher,
-// cdf, inverse-CDF draws, sort, merge, compositing) is executed identically by both slots of a ray — same inputs, same order,
-// same results, so the arithmetic contract and the accumulation order are untouched — and only the decode differs: after
-// it the two slots exchange sigma / skipped flag / their 16 colour channels (ds_bpermute), then both consume sample A and
-// sample B in order.  Slot 0 writes the outputs.  No dumps on this path (the host falls back to k_render for them).
-// =====================================================================================================================
-// FAST (P3D_FLAG_FAST_COLOR): the final pass decodes in tolerance mode exactly as k_render<…, FAST = true> does (two-term f16 MLP
-// operands, hardware transcendentals, the exact mask guard, rays dropped below a transmittance of 2e-6); the coarse pass, and
-// with it every importance draw, stays on the exact contract.
-template <int NF, bool FAST>
-__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, 1) void k_render_pair(RenderParams p) {  // 1 workgroup per CU is all a small launch has: up to 512 VGPRs
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    p3d_load_mlp_to_lds(lds, p.w0, p.b0, p.w1, p.b1, !FAST);
-    if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-    const int jr = j & 15, slot = j >> 4;
-    const int nwaves = blockDim.x >> 6;
-    long long tile = (long long)blockIdx.x * nwaves + wave;  // 16-ray tiles
-    if (tile >= p.ntiles) return;  // no workgroup barrier below this line
-    float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * 32;
+// v of lane ^ X within each half-wave (X < 32): ds_swizzle in bit mode (and 0x1f, or 0, xor X) — the crossbar, no address VGPR
+template <int X>
+P3D_DEV float p3d_lane_xor(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x1f | (X << 10)));
+}
 
-    const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
-    long long n = tile / p.tiles_per_img, tl = tile - n * p.tiles_per_img;
-    long long r;
-    if (p.tile_w > 0) {  // 4x4 pixel tile, Morton lane order
-        long long ty = tl / p.tiles_x, tx = tl - ty * p.tiles_x;
-        const int lx = (jr & 1) | ((jr >> 1) & 2), ly = ((jr >> 1) & 1) | ((jr >> 2) & 2);
-        r = (ty * 4 + ly) * p.tile_w + tx * 4 + lx;
+// x[k] of a 2- or 4-entry register array by selects of VALUES (a dynamic index, or a select of the entries' addresses, puts the
+// array in scratch)
+template <int N>
+P3D_DEV float p3d_select(const float (&x)[N], int k) {
+    static_assert(N == 2 || N == 4, "two or four entries");
+    const float x0 = x[0], x1 = x[1];
+    if constexpr (N == 2) {
+        return (k & 1) ? x1 : x0;
     } else {
-        r = tl * 16 + jr;
-    }
-    const bool active = r < p.R;
-    const long long rc = active ? r : p.R - 1;
-    const size_t ray = (size_t)n * p.R + rc;
-
-    P3dPlaneGeom g;
-    g.halfW = 0.5f * (float)p.W; g.halfH = 0.5f * (float)p.H; g.fW = (float)p.W; g.fH = (float)p.H; g.W = p.W;
-    g.plane_bytes = (uint32_t)p.H * (uint32_t)p.W * 128u;
-    unsigned nlo = __builtin_amdgcn_readfirstlane((unsigned)n);
-    const float* pbase = p.planes + ((p.cfg.flags & P3D_FLAG_SHARED_PLANES) ? (size_t)0 : (size_t)nlo * 3 * (g.plane_bytes / 4));
-    auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)pbase, 0, 3 * g.plane_bytes, 0x00020000);
-    const P3dDecodeCfg cfg = p.cfg;
-    const bool early = !(cfg.flags & P3D_FLAG_NO_EARLY_OUT);
-    const bool f_crop = (cfg.flags & P3D_FLAG_CROP) != 0;
-    int ndec = 0;
-    // value of the partner slot (lane ^ 16): ds_swizzle bit mode and 0x1f, or 0, xor 0x10 — the crossbar, no address VGPR
-    auto partner = [](float v) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401f));
-    };
-
-    const float ox = p.rays_o[ray * 3], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
-    const float dx = p.rays_d[ray * 3], dy = p.rays_d[ray * 3 + 1], dz = p.rays_d[ray * 3 + 2];
-
-    // LDS rows of this wave: row(i)[jr]; both slots of a ray write the same values
-    float* tcA = wl;
-    float* wcA = tcA + Sc * 32;
-    float* tfA = (NF > 0) ? wcA : wcA + Sc * 32;
-
-    bool unsorted = false;
-    {
-        const float step = (p.ray_end - p.ray_start) / (float)(Sc - 1);
-        const float* jit = p.jitter + ray * Sc;
-        const bool limits = p.ray_start_arr != nullptr;  // per-ray limits: as in k_render
-        const float rs = limits ? p.ray_start_arr[ray] : 0.0f, span = limits ? p.ray_end_arr[ray] - rs : 0.0f;
-        const float rdelta = span / (float)(Sc - 1);
-        float prev = -__builtin_inff();
-        for (int i = 0; i < Sc; ++i) {
-            float lin = (i < Sc / 2) ? p3d_fma(step, (float)i, p.ray_start) : p3d_fma(-step, (float)(Sc - 1 - i), p.ray_end);
-            const float ji = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 0u, ray, i) : jit[i];
-            float t = lin + ji * p.depth_delta;
-            if (limits) {
-                const float prod = ((float)i / (float)(Sc - 1)) * span;
-                t = (rs + prod) + ji * rdelta;
-            } else if (p.disparity) {
-                const float s01 = 1.0f / (float)(Sc - 1);
-                const float l01 = (i < Sc / 2) ? p3d_fma(s01, (float)i, 0.0f) : p3d_fma(-s01, (float)(Sc - 1 - i), 1.0f);
-                const float dd = l01 + ji * p.depth_delta;
-                const float ta_ = p.ray_start * (1.0f - dd), tb_ = p.ray_end * dd;
-                t = 1.0f / (ta_ + tb_);
-            }
-            tcA[i * 32 + jr] = t;
-            unsorted |= (t < prev);
-            prev = t;
-        }
-    }
-    float tmin = __builtin_inff(), tmax = -__builtin_inff();
-    auto is_cropped = [&](float px, float pz) {
-        return f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit);
-    };
-    if (Sf > 0) {
-        // ---- coarse pass, two samples per step
-        MarchState st;
-        st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
-        for (int i = 0; i < Sc; i += 2) {
-            const bool haveB = i + 1 < Sc;  // uniform
-            const float tA = tcA[i * 32 + jr], tB = tcA[(haveB ? i + 1 : i) * 32 + jr];
-            const float t = slot ? tB : tA;
-            const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;
-            float sigma = P3D_SIGMA_MASKED;
-            bool skip = false, live = true;
-            if (early) {
-                live = !(is_cropped(px, pz) || st.Td < 1e-60);  // slot 1: Td before sample A's interval — conservative, still exact
-                skip = __builtin_amdgcn_ballot_w64(live) == 0;
-            }
-            if (!skip) {
-                f32x16 dummy;
-                p3d_decode_wave<false, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
-                ndec += 1;
-            }
-            const float so = partner(sigma);
-            const float sA = slot ? so : sigma, sB = slot ? sigma : so;
-            if (i > 0) {
-                float tm;
-                wcA[(i - 1) * 32 + jr] = p3d_march_weight(st, tA, sA, tm);
-            }
-            st.prev_t = tA; st.prev_sigma = sA;
-            if (haveB) {
-                float tm;
-                wcA[i * 32 + jr] = p3d_march_weight(st, tB, sB, tm);
-                st.prev_t = tB; st.prev_sigma = sB;
-            }
-        }
-        const int Ns = Sc - 3;
-        {
-            double sum = 0.0;
-            float wa = wcA[0 * 32 + jr], wb = wcA[1 * 32 + jr];
-            for (int jj = 0; jj < Ns; ++jj) {
-                float wc = wcA[(jj + 2) * 32 + jr];
-                float m1 = __builtin_fmaxf(wa, wb), m2 = __builtin_fmaxf(wb, wc);
-                float v = ((m1 + m2) * 0.5f + 0.01f) + 1e-5f;
-                sum += (double)v;
-                wcA[(jj + 1) * 32 + jr] = v;
-                wa = wb; wb = wc;
-            }
-            float fsum = (float)sum;
-            double acc = 0.0;
-            wcA[jr] = 0.0f;
-            for (int jj = 0; jj < Ns; ++jj) {
-                float pdf = wcA[(jj + 1) * 32 + jr] / fsum;
-                acc += (double)pdf;
-                wcA[(jj + 1) * 32 + jr] = (float)acc;
-            }
-        }
-        const float* uu = p.u + ray * Sf;
-        if constexpr (NF > 0) {
-            // as in k_render: every load of the row issued before the first search, eight draws in lock-step (the eight LDS
-            // reads of a search step in flight together; one draw at a time was a chain of 8 dependent LDS round trips x Sf)
-            constexpr int DB = 8;
-            float tf[NF];
-#pragma unroll
-            for (int i = 0; i < NF; ++i) tf[i] = (i < Sf) ? (p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i]) : 0.0f;
-#pragma unroll
-            for (int i0 = 0; i0 < NF; i0 += DB) {
-                if (i0 < Sf) {  // wave-uniform
-                    float ub[DB], vb[DB];
-                    int kb[DB];
-#pragma unroll
-                    for (int q = 0; q < DB; ++q) ub[q] = tf[i0 + q];
-                    p3d_inverse_cdf_batch<DB>(wcA, tcA, Ns, jr, ub, vb, kb);
-#pragma unroll
-                    for (int q = 0; q < DB; ++q) tf[i0 + q] = (i0 + q < Sf) ? vb[q] : __builtin_inff();
-                } else {
-#pragma unroll
-                    for (int q = 0; q < DB; ++q) tf[i0 + q] = __builtin_inff();
-                }
-            }
-            p3d_sort_network<NF>(tf);
-#pragma unroll
-            for (int i = 0; i < NF; ++i)
-                if (i < Sf) tfA[i * 32 + jr] = tf[i];
-        } else {
-            // the generic path sorts in LDS: only slot 0 may move the keys (both slots of a ray share the column)
-            float* tmpA = tfA;
-            for (int i = 0; i < Sf; ++i) {
-                int k;
-                float v = p3d_inverse_cdf(wcA, tcA, Ns, jr, p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i], k);
-                tmpA[i * 32 + jr] = v;
-            }
-            if (slot == 0 && h == 0) p3d_lds_insertion_sort(tfA, Sf, jr);
-        }
-        if (__builtin_amdgcn_ballot_w64(unsorted) != 0 && slot == 0 && h == 0) p3d_lds_insertion_sort(tcA, Sc, jr);
-    }
-    // ---- final pass: two merged samples per step
-    MarchState st;
-    st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
-    f32x16 C, prev_rgb;
-    float Cx = 0.0f, Cy = 0.0f, Cz = 0.0f, ppx = 0.0f, ppy = 0.0f, ppz = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) { C[c] = 0.0f; prev_rgb[c] = 0.0f; }
-    {
-        int ci = 0, fi = 0;
-        float ta = tcA[jr], tb = (Sf > 0) ? tfA[jr] : __builtin_inff();
-        bool prev_skipped = false;
-        auto next_depth = [&]() {  // unify_samples' merge: ties take the coarse sample first (stable sort)
-            const bool take_c = (ci < Sc) && (fi >= Sf || ta <= tb);
-            const float t = take_c ? ta : tb;
-            ci += take_c ? 1 : 0;
-            fi += take_c ? 0 : 1;
-            const int cq = ci < Sc ? ci : Sc - 1, fq = fi < Sf ? fi : (Sf > 0 ? Sf - 1 : 0);
-            const float nv = (take_c ? tcA : tfA)[(take_c ? cq : fq) * 32 + jr];  // (selects, not a store through a selected pointer)
-            ta = take_c ? nv : ta;
-            tb = take_c ? tb : nv;
-            tmin = __builtin_fminf(tmin, t);
-            tmax = __builtin_fmaxf(tmax, t);
-            return t;
-        };
-        // the second half of k_render's loop body, for one sample whose decode (or skip) has already happened
-        auto consume = [&](int m, float t, float px, float py, float pz, float sigma, f32x16 rgb, bool skipped) {
-            if (m > 0) {
-                float tm;
-                float w = p3d_march_weight(st, t, sigma, tm);
-                if (early) {
-                    if (__builtin_amdgcn_ballot_w64(prev_skipped && w != 0.0f) != 0) {
-                        float s2;
-                        f32x16 c2;
-                        if constexpr (FAST) p3d_decode_wave_fast<true, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
-                        else p3d_decode_wave<true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
-                        if (prev_skipped) prev_rgb = c2;
-                        prev_skipped = false;
-                    }
-                    if (__builtin_amdgcn_ballot_w64(skipped && w != 0.0f) != 0) {
-                        float s2;
-                        if constexpr (FAST) p3d_decode_wave_fast<true, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, s2, rgb);
-                        else p3d_decode_wave<true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
-                        skipped = false;
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < 16; ++c) C[c] = p3d_fma(w, (prev_rgb[c] + rgb[c]) * 0.5f, C[c]);
-                Cx = p3d_fma(w, (ppx + px) * 0.5f, Cx);
-                Cy = p3d_fma(w, (ppy + py) * 0.5f, Cy);
-                Cz = p3d_fma(w, (ppz + pz) * 0.5f, Cz);
-                st.W = st.W + w;
-                st.D = p3d_fma(w, tm, st.D);
-            }
-            st.prev_t = t; st.prev_sigma = sigma;
-            prev_rgb = rgb;
-            prev_skipped = skipped;
-            ppx = px; ppy = py; ppz = pz;
-        };
-        for (int m = 0; m < S; m += 2) {
-            const bool haveB = m + 1 < S;  // uniform
-            const float tA = next_depth();
-            const float tB = haveB ? next_depth() : tA;
-            const float pxA = ox + tA * dx, pyA = oy + tA * dy, pzA = oz + tA * dz;
-            const float pxB = ox + tB * dx, pyB = oy + tB * dy, pzB = oz + tB * dz;
-            const float px = slot ? pxB : pxA, py = slot ? pyB : pyA, pz = slot ? pzB : pzA;
-            float sigma = P3D_SIGMA_MASKED;
-            f32x16 rgb;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) rgb[c] = 0.0f;
-            bool skipped = false, live = true;
-            if (early) {
-                // exact mode: below 1e-60 every later weight is exactly 0.  Tolerance mode: the transmittance bounds what the rest
-                // of the ray can still add — stop at 2e-6, inside the 2e-5 budget (as in k_render)
-                live = !(is_cropped(px, pz) || st.Td < (FAST ? 2e-6 : 1e-60));
-                skipped = __builtin_amdgcn_ballot_w64(live) == 0;
-            }
-            if (!skipped) {
-                if constexpr (FAST) p3d_decode_wave_fast<true, P3D_QUAD_PAIR != 0, false, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
-                else p3d_decode_wave<true, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
-                ndec += 1;
-                skipped = !live;
-            }
-            // exchange: every lane gets both samples of its ray (its own channel half)
-            const float so = partner(sigma);
-            const float sA = slot ? so : sigma, sB = slot ? sigma : so;
-            const int ko = __builtin_amdgcn_ds_swizzle((int)skipped, 0x401f);
-            const int kA = slot ? ko : (int)skipped, kB = slot ? (int)skipped : ko;
-            f32x16 rgbA, rgbB;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const float other = partner(rgb[c]);
-                rgbA[c] = slot ? other : rgb[c];
-                rgbB[c] = slot ? rgb[c] : other;
-            }
-            consume(m, tA, pxA, pyA, pzA, sA, rgbA, kA != 0);
-            if (haveB) consume(m + 1, tB, pxB, pyB, pzB, sB, rgbB, kB != 0);
-        }
-    }
-    {
-        const float Wt = st.W;
-        float d = st.D / Wt;
-        if (d != d) d = __builtin_inff();
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            float v = C[c];
-            if (p.white_back) v = (v + 1.0f) - Wt;
-            C[c] = v * 2.0f - 1.0f;
-        }
-        if (p.white_back) { Cx = (Cx + 1.0f) - Wt; Cy = (Cy + 1.0f) - Wt; Cz = (Cz + 1.0f) - Wt; }
-        Cx = Cx * 2.0f - 1.0f; Cy = Cy * 2.0f - 1.0f; Cz = Cz * 2.0f - 1.0f;
-        if (active && slot == 0) {
-            float* dst = p.out_feat + ray * 32 + 4 * h;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *(f32x4*)(dst + 8 * q) = (f32x4){C[4 * q], C[4 * q + 1], C[4 * q + 2], C[4 * q + 3]};
-            if (h == 0) {
-                p.out_depth[ray] = d;
-                p.out_wsum[ray] = Wt;
-                p.out_xyz[ray * 3] = Cx; p.out_xyz[ray * 3 + 1] = Cy; p.out_xyz[ray * 3 + 2] = Cz;
-            }
-        }
-    }
-    if (!active) { tmin = __builtin_inff(); tmax = -__builtin_inff(); }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        tmin = __builtin_fminf(tmin, __shfl_xor(tmin, o));
-        tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, o));
-    }
-    if (lane == 0) {
-        atomicMin(p.gminmax, p3d_f2ord(tmin));
-        atomicMax(p.gminmax + 1, p3d_f2ord(tmax));
-        if (p.per_view_clamp) {
-            atomicMin(p.gminmax + 4 + 2 * nlo, p3d_f2ord(tmin));
-            atomicMax(p.gminmax + 5 + 2 * nlo, p3d_f2ord(tmax));
-        }
-        atomicAdd((unsigned long long*)(p.gminmax + 2), (unsigned long long)ndec);
+        const float x2 = x[2], x3 = x[3];
+        return (k & 2) ? ((k & 1) ? x3 : x2) : ((k & 1) ? x1 : x0);
     }
 }
 
 // =====================================================================================================================
-// k_render_quad (round 4): the small-launch kernel with 8 rays x 4 sample slots per wave — lane = ray (j & 7) x slot (j >> 3) x
-// channel half — so that a 128^2-ray view makes 2048 waves = TWO per SIMD (k_render_pair: 1024, one per SIMD, every step's
-// bookkeeping exposed latency: ~4 us per step whether it decodes or not, profiles/history/r03_notes.txt).  Per-wave LDS rows hold 8 rays
-// (32 bytes per row instead of 128: 6.6 KB per wave at 96+96).  Everything per ray is executed identically by the ray's eight
-// lanes, as in k_render_pair; a step decodes four consecutive samples of every ray; sigma and the skipped flag are exchanged to
-// all lanes of the ray, the 16 colour channels only towards slot 0, whose lanes write the outputs.  Bit-identical to k_render.
-// =====================================================================================================================
-// WO ("weights only", P3D_FLAG_WEIGHTS_ONLY; tolerance-mode instantiations only): the launch is asked for the accumulated opacity
-// (wsum) and depth alone — the occlusion pass of paste_front (training/triplane.py:565-578 reads `image_weights` of a second render and
-// nothing else).  A ray's weights depend on depths and densities only, so the final pass decodes DENSITIES (layer 1 + the sigma row, the
-// coarse pass's cost), exchanges no colours, runs no colour guards and composites nothing but W and D: wsum and depth are bit-identical
-// to the full launch's, feat / xyz are not written.
-template <int NF, bool FAST, bool WO = false>
-// Registers: the tolerance-mode instantiations are compiled for two waves per SIMD (<= 256 registers; 128^2 rays = 2048 waves).  The
-// EXACT ones are compiled for one (512): under the 256-register cap they spilled 108-127 VGPRs (164-176 B of scratch per lane, round 4),
-// and the host picks the exact quad kernel only for launches of <= 8192 rays = <= 1024 waves — one per SIMD whatever the cap.
-__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_quad(RenderParams p) {
-    static_assert(!WO || FAST, "the weights-only launch exists for the tolerance mode (the renderer class's default, what the paste runs)");
+// k_render_slots: the same algorithm for SMALL launches (fewer 32-ray tiles than the chip has SIMDs, e.g. the pipeline's single
+// 128^2-ray views: 512 tiles on 1024 SIMDs, each wave alone on its SIMD and ALU-bound at ~4.7 us per decode step).  A wave owns
+// RPW = 32 / SLOTS rays and decodes SLOTS consecutive samples of every ray per step: lane j = ray (j % RPW) x sample slot (j / RPW)
+// x channel half, so a launch makes SLOTS times as many waves, each with 1 / SLOTS of the decode steps.  SLOTS = 2: a 128^2-ray
+// view makes 1024 waves, one per SIMD.  SLOTS = 4 (round 4): 2048 waves = TWO per SIMD (with two slots every step's bookkeeping
+// was exposed latency: ~4 us per step whether it decodes or not, profiles/history/r03_notes.txt).  Per-wave LDS rows hold the
+// wave's RPW rays (6.6 KB per wave at 96+96 with four slots).
+// Everything per ray (depth rows in LDS, marcher, cdf, inverse-CDF draws, sort, merge, compositing) is executed identically by
+// all lanes of the ray — same inputs, same order, same results, so the arithmetic contract and the accumulation order are
+// untouched — and only the decode differs: after it the lanes exchange sigma and the skipped flag to every lane of the ray (the
+// marcher state — transmittance, weights, the guards' decisions — is identical on them) and the 16 colour channels only towards
+// slot 0, whose lanes write the outputs; the other slots accumulate colours in another order and never store them (48 crossbar
+// moves per step with four slots instead of 48 + 192 selects).  Then every lane consumes the step's samples in order.
+// Bit-identical to k_render.  No dumps on this path (the host falls back to k_render for them).
+// FAST (P3D_FLAG_FAST_COLOR): the final pass decodes in tolerance mode exactly as k_render<…, FAST = true> does (two-term f16 MLP
+// operands, hardware transcendentals, the exact mask guard, rays dropped below a transmittance of 2e-6); the coarse pass, and
+// with it every importance draw, stays on the exact contract.
+// WO ("weights only", P3D_FLAG_WEIGHTS_ONLY; four-slot tolerance-mode instantiations only): the launch is asked for the accumulated
+// opacity (wsum) and depth alone — the occlusion pass of paste_front (training/triplane.py:565-578 reads `image_weights` of a second
+// render and nothing else).  A ray's weights depend on depths and densities only, so the final pass decodes DENSITIES (layer 1 + the
+// sigma row, the coarse pass's cost), exchanges no colours, runs no colour guards and composites nothing but W and D: wsum and depth
+// are bit-identical to the full launch's, feat / xyz are not written.
+// Registers: one workgroup per CU is all a small launch has, and every instantiation but the four-slot tolerance ones is compiled for
+// one wave per SIMD (up to 512 registers).  The four-slot tolerance ones are compiled for two (<= 256 registers; 128^2 rays = 2048
+// waves).  The EXACT four-slot ones under the 256-register cap spilled 108-127 VGPRs (164-176 B of scratch per lane, round 4), and
+// the host picks them only for launches of <= 8192 rays = <= 1024 waves — one per SIMD whatever the cap.
+template <int SLOTS, int NF, bool FAST, bool WO = false>
+__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, (SLOTS == 4 && FAST) ? 2 : 1) void k_render_slots(RenderParams p) {
+    static_assert(SLOTS == 2 || SLOTS == 4, "16 rays x 2 slots or 8 rays x 4 slots per wave");
+    static_assert(!WO || (FAST && SLOTS == 4), "the weights-only launch exists for the tolerance mode (the renderer class's default, what the paste runs)");
+    constexpr int RPW = 32 / SLOTS;  // rays per wave
+    constexpr int RS = RPW;          // floats per LDS row
     extern __shared__ __attribute__((aligned(16))) float lds[];
     p3d_load_mlp_to_lds(lds, p.w0, p.b0, p.w1, p.b1, !FAST);
     if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-    const int jr = j & 7, slot = j >> 3;  // ray of the wave (8), sample slot (4)
-    constexpr int RS = 8;                 // floats per LDS row
+    const int jr = j % RPW, slot = j / RPW;  // ray of the wave, sample slot
     const int nwaves = blockDim.x >> 6;
-    long long tile = (long long)blockIdx.x * nwaves + wave;  // 8-ray tiles
+    long long tile = (long long)blockIdx.x * nwaves + wave;  // RPW-ray tiles
     if (tile >= p.ntiles) return;  // no workgroup barrier below this line
     float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * RS;
 
     const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
     long long n = tile / p.tiles_per_img, tl = tile - n * p.tiles_per_img;
     long long r;
-    if (p.tile_w > 0) {  // 4x2 pixel tile, Morton lane order (a lane quad = a 2x2 pixel block: the quad-cooperative gathers)
+    if (p.tile_w > 0) {  // 4 x (RPW / 4) pixel tile, Morton lane order (a lane quad = a 2x2 pixel block: the quad-cooperative gathers)
         long long ty = tl / p.tiles_x, tx = tl - ty * p.tiles_x;
-        const int lx = (jr & 1) | ((jr >> 1) & 2), ly = (jr >> 1) & 1;
-        r = (ty * 2 + ly) * p.tile_w + tx * 4 + lx;
+        const int lx = (jr & 1) | ((jr >> 1) & 2), ly = ((jr >> 1) & 1) | ((jr >> 2) & 2);
+        r = (ty * (RPW / 4) + ly) * p.tile_w + tx * 4 + lx;
     } else {
-        r = tl * 8 + jr;
+        r = tl * RPW + jr;
     }
     const bool active = r < p.R;
     const long long rc = active ? r : p.R - 1;
@@ -1518,23 +1169,29 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
     const bool early = !(cfg.flags & P3D_FLAG_NO_EARLY_OUT);
     const bool f_crop = (cfg.flags & P3D_FLAG_CROP) != 0;
     int ndec = 0;
-    // value of the lane whose slot differs by X (lane ^ 8X): ds_swizzle bit mode (and 0x1f, or 0, xor 8X) — the crossbar, no address VGPR
-    auto swz8 = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x201f)); };
-    auto swz16 = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401f)); };
-    auto swz24 = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x601f)); };
-    // the value of sample slot q of this lane's ray, on EVERY lane of the ray: the lane whose slot is q sits at lane ^ 8 (slot ^ q)
-    auto of_slot = [&](int qq, float own, float x8, float x16, float x24) {
-        const int k = slot ^ qq;
-        return (k & 1) ? ((k & 2) ? x24 : x8) : ((k & 2) ? x16 : own);
+    // xk = v of the lane whose slot differs by k (lane ^ RPW k; x2, x3: four slots only).  Scalars rather than an array, and
+    // of_slot's select tree rather than p3d_select's: with those the four-slot instantiations spilled SGPRs or allocated scratch.
+    struct Slots { float x0, x1, x2, x3; };
+    auto exchange = [](float v) {
+        Slots s{v, p3d_lane_xor<RPW>(v), v, v};
+        if constexpr (SLOTS == 4) { s.x2 = p3d_lane_xor<2 * RPW>(v); s.x3 = p3d_lane_xor<3 * RPW>(v); }
+        return s;
+    };
+    // the value of sample slot q of this lane's ray, on EVERY lane of the ray, from exchange(): the lane whose slot is q sits at
+    // lane ^ RPW (slot ^ q)
+    auto of_slot = [&](int q, Slots s) {
+        const int k = slot ^ q;
+        return (k & 1) ? ((k & 2) ? s.x3 : s.x1) : ((k & 2) ? s.x2 : s.x0);
     };
 
     const float ox = p.rays_o[ray * 3], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
     const float dx = p.rays_d[ray * 3], dy = p.rays_d[ray * 3 + 1], dz = p.rays_d[ray * 3 + 2];
 
-    // LDS rows of this wave: row(i)[jr]; both slots of a ray write the same values
+    // LDS rows of this wave: row(i)[jr]; all slots of a ray write the same values
     float* tcA = wl;
     float* wcA = tcA + Sc * RS;
     float* tfA = (NF > 0) ? wcA : wcA + Sc * RS;
+    auto tc_lds = [&](int i) { return tcA[i * RS + jr]; };
 
     bool unsorted = false;
     {
@@ -1568,19 +1225,19 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
         return f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit);
     };
     if (Sf > 0) {
-        // ---- coarse pass, four samples per step
+        // ---- coarse pass, SLOTS samples per step
         MarchState st;
         st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
-        for (int i = 0; i < Sc; i += 4) {
-            float tq[4];
+        for (int i = 0; i < Sc; i += SLOTS) {
+            float tq[SLOTS];
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) tq[qq] = tcA[(i + qq < Sc ? i + qq : Sc - 1) * RS + jr];
-            const float t = (slot & 2) ? ((slot & 1) ? tq[3] : tq[2]) : ((slot & 1) ? tq[1] : tq[0]);
+            for (int q = 0; q < SLOTS; ++q) tq[q] = tcA[(i + q < Sc ? i + q : Sc - 1) * RS + jr];
+            const float t = p3d_select(tq, slot);
             const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;
             float sigma = P3D_SIGMA_MASKED;
             bool skip = false, live = true;
             if (early) {
-                live = !(is_cropped(px, pz) || st.Td < 1e-60);  // slots 1-3: Td before the step's first interval — conservative, still exact
+                live = !(is_cropped(px, pz) || st.Td < 1e-60);  // slots > 0: Td before the step's first interval — conservative, still exact
                 skip = __builtin_amdgcn_ballot_w64(live) == 0;
             }
             if (!skip) {
@@ -1588,16 +1245,16 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
                 p3d_decode_wave<false, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
                 ndec += 1;
             }
-            const float s8 = swz8(sigma), s16 = swz16(sigma), s24 = swz24(sigma);
+            const Slots sx = exchange(sigma);
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                if (i + qq < Sc) {  // uniform
-                    const float sq = of_slot(qq, sigma, s8, s16, s24);
-                    if (i + qq > 0) {
+            for (int q = 0; q < SLOTS; ++q) {
+                if (i + q < Sc) {  // uniform
+                    const float sq = of_slot(q, sx);
+                    if (i + q > 0) {
                         float tm;
-                        wcA[(i + qq - 1) * RS + jr] = p3d_march_weight(st, tq[qq], sq, tm);
+                        wcA[(i + q - 1) * RS + jr] = p3d_march_weight(st, tq[q], sq, tm);
                     }
-                    st.prev_t = tq[qq]; st.prev_sigma = sq;
+                    st.prev_t = tq[q]; st.prev_sigma = sq;
                 }
             }
         }
@@ -1637,7 +1294,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
                     int kb[DB];
 #pragma unroll
                     for (int q = 0; q < DB; ++q) ub[q] = tf[i0 + q];
-                    p3d_inverse_cdf_batch<DB, RS>(wcA, tcA, Ns, jr, ub, vb, kb);
+                    p3d_inverse_cdf<DB, RS>(wcA, tc_lds, Ns, jr, ub, vb, kb);
 #pragma unroll
                     for (int q = 0; q < DB; ++q) tf[i0 + q] = (i0 + q < Sf) ? vb[q] : __builtin_inff();
                 } else {
@@ -1650,18 +1307,19 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
             for (int i = 0; i < NF; ++i)
                 if (i < Sf) tfA[i * RS + jr] = tf[i];
         } else {
-            // the generic path sorts in LDS: only slot 0 may move the keys (both slots of a ray share the column)
-            float* tmpA = tfA;
+            // the generic path sorts in LDS: only slot 0 may move the keys (all slots of a ray share the column)
             for (int i = 0; i < Sf; ++i) {
-                int k;
-                float v = p3d_inverse_cdf<RS>(wcA, tcA, Ns, jr, p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i], k);
-                tmpA[i * RS + jr] = v;
+                const float ui[1] = {p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i]};
+                float v[1];
+                int k[1];
+                p3d_inverse_cdf<1, RS>(wcA, tc_lds, Ns, jr, ui, v, k);
+                tfA[i * RS + jr] = v[0];
             }
             if (slot == 0 && h == 0) p3d_lds_insertion_sort<RS>(tfA, Sf, jr);
         }
         if (__builtin_amdgcn_ballot_w64(unsorted) != 0 && slot == 0 && h == 0) p3d_lds_insertion_sort<RS>(tcA, Sc, jr);
     }
-    // ---- final pass: four merged samples per step
+    // ---- final pass: SLOTS merged samples per step
     MarchState st;
     st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
     f32x16 C, prev_rgb;
@@ -1721,22 +1379,22 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
             prev_skipped = skipped;
             ppx = px; ppy = py; ppz = pz;
         };
-        for (int m = 0; m < S; m += 4) {
-            float tq[4], pxq[4], pyq[4], pzq[4];
+        for (int m = 0; m < S; m += SLOTS) {
+            float tq[SLOTS], pxq[SLOTS], pyq[SLOTS], pzq[SLOTS];
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                tq[qq] = (m + qq < S) ? next_depth() : tq[qq > 0 ? qq - 1 : 0];  // (uniform condition)
-                pxq[qq] = ox + tq[qq] * dx; pyq[qq] = oy + tq[qq] * dy; pzq[qq] = oz + tq[qq] * dz;
+            for (int q = 0; q < SLOTS; ++q) {
+                tq[q] = (m + q < S) ? next_depth() : tq[q > 0 ? q - 1 : 0];  // (uniform condition)
+                pxq[q] = ox + tq[q] * dx; pyq[q] = oy + tq[q] * dy; pzq[q] = oz + tq[q] * dz;
             }
-            const float px = (slot & 2) ? ((slot & 1) ? pxq[3] : pxq[2]) : ((slot & 1) ? pxq[1] : pxq[0]);
-            const float py = (slot & 2) ? ((slot & 1) ? pyq[3] : pyq[2]) : ((slot & 1) ? pyq[1] : pyq[0]);
-            const float pz = (slot & 2) ? ((slot & 1) ? pzq[3] : pzq[2]) : ((slot & 1) ? pzq[1] : pzq[0]);
+            const float px = p3d_select(pxq, slot), py = p3d_select(pyq, slot), pz = p3d_select(pzq, slot);
             float sigma = P3D_SIGMA_MASKED;
             f32x16 rgb;
 #pragma unroll
             for (int c = 0; c < 16; ++c) rgb[c] = 0.0f;
             bool skipped = false, live = true;
             if (early) {
+                // exact mode: below 1e-60 every later weight is exactly 0.  Tolerance mode: the transmittance bounds what the rest
+                // of the ray can still add — stop at 2e-6, inside the 2e-5 budget (as in k_render)
                 live = !(is_cropped(px, pz) || st.Td < (FAST ? 2e-6 : 1e-60));
                 skipped = __builtin_amdgcn_ballot_w64(live) == 0;
             }
@@ -1746,22 +1404,20 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, FAST ? 2 : 1) void k_render_
                 ndec += 1;
                 skipped = !live;
             }
-            // exchange.  sigma and the skipped flag: every lane of the ray gets all four (the marcher state — transmittance, weights,
-            // the guards' decisions — is identical on the ray's lanes).  The colours: lane ^ 8q holds sample q only for the slot-0
-            // lanes, which are the ones that write the ray's outputs; the other slots accumulate colours in another order and never
-            // store them (48 crossbar moves per step instead of 48 + 192 selects).
-            const float s8 = swz8(sigma), s16 = swz16(sigma), s24 = swz24(sigma);
-            const float kf = skipped ? 1.0f : 0.0f;
-            const float k8 = swz8(kf), k16 = swz16(kf), k24 = swz24(kf);
-            f32x16 r8 = rgb, r16 = rgb, r24 = rgb;
+            // exchange (see the header): sigma and the skipped flag to every lane of the ray; the colours of sample q at
+            // lane ^ RPW q, which holds them only for the slot-0 lanes
+            const Slots sx = exchange(sigma), kx = exchange(skipped ? 1.0f : 0.0f);
+            f32x16 r1 = rgb, r2 = rgb, r3 = rgb;
             if constexpr (!WO) {
 #pragma unroll
-                for (int c = 0; c < 16; ++c) { r8[c] = swz8(rgb[c]); r16[c] = swz16(rgb[c]); r24[c] = swz24(rgb[c]); }
+                for (int c = 0; c < 16; ++c) { const Slots x = exchange(rgb[c]); r1[c] = x.x1; r2[c] = x.x2; r3[c] = x.x3; }
             }
-            consume(m, tq[0], pxq[0], pyq[0], pzq[0], of_slot(0, sigma, s8, s16, s24), rgb, of_slot(0, kf, k8, k16, k24) != 0.0f);
-            if (m + 1 < S) consume(m + 1, tq[1], pxq[1], pyq[1], pzq[1], of_slot(1, sigma, s8, s16, s24), r8, of_slot(1, kf, k8, k16, k24) != 0.0f);
-            if (m + 2 < S) consume(m + 2, tq[2], pxq[2], pyq[2], pzq[2], of_slot(2, sigma, s8, s16, s24), r16, of_slot(2, kf, k8, k16, k24) != 0.0f);
-            if (m + 3 < S) consume(m + 3, tq[3], pxq[3], pyq[3], pzq[3], of_slot(3, sigma, s8, s16, s24), r24, of_slot(3, kf, k8, k16, k24) != 0.0f);
+            consume(m, tq[0], pxq[0], pyq[0], pzq[0], of_slot(0, sx), rgb, of_slot(0, kx) != 0.0f);
+            if (m + 1 < S) consume(m + 1, tq[1], pxq[1], pyq[1], pzq[1], of_slot(1, sx), r1, of_slot(1, kx) != 0.0f);
+            if constexpr (SLOTS == 4) {
+                if (m + 2 < S) consume(m + 2, tq[2], pxq[2], pyq[2], pzq[2], of_slot(2, sx), r2, of_slot(2, kx) != 0.0f);
+                if (m + 3 < S) consume(m + 3, tq[3], pxq[3], pyq[3], pzq[3], of_slot(3, sx), r3, of_slot(3, kx) != 0.0f);
+            }
         }
     }
     {
@@ -2032,6 +1688,20 @@ static hipError_t p3d_ensure_dynamic_lds(K kernel, size_t bytes) {
         while (cur < bytes && !g.compare_exchange_weak(cur, bytes, std::memory_order_release)) {}
     }
     return e;
+}
+
+// Calls f(std::integral_constant<int, NF>()) with the fine-depth capacity nf of a render launch (48, 64, 96, or 0: the generic path)
+template <typename F>
+static int p3d_with_nf(int nf, F f) {
+#ifdef P3D_ONLY_NF  // development builds (tools/resource_usage.py -D P3D_ONLY_NF=48): compile ONE fine-depth capacity
+    (void)nf;
+    return f(std::integral_constant<int, P3D_ONLY_NF>());
+#else
+    if (nf == 48) return f(std::integral_constant<int, 48>());
+    if (nf == 64) return f(std::integral_constant<int, 64>());
+    if (nf == 96) return f(std::integral_constant<int, 96>());
+    return f(std::integral_constant<int, 0>());
+#endif
 }
 
 static P3dDecodeCfg make_cfg(const p3d_opts* o) {
@@ -2306,9 +1976,9 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
         if (nwaves == 1) return P3D_E_RANGE;
     }
     hipLaunchKernelGGL(k_minmax_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, p.gminmax, p.per_view_clamp ? N : 0);
-    // small launches: 16 rays x 2 samples per wave (k_render_pair) while its waves still fit in ONE round on the 1024 SIMDs
+    // small launches: 16 rays x 2 samples per wave (k_render_slots<2, ...>) while its waves still fit in ONE round on the 1024 SIMDs
     // (measured at 48+48: 128^2 rays 0.74 -> 0.49 ms, but 192^2 = 1152 tiles 0.99 -> 1.28 ms: its steps are ~30 % dearer)
-    // ... and of those, 8 rays x 4 samples per wave (k_render_quad) where it measured faster (profiles/r04_notes.txt): launches of at
+    // ... and of those, 8 rays x 4 samples per wave (k_render_slots<4, ...>) where it measured faster (profiles/r04_notes.txt): launches of at
     // most 8192 rays — fewer 16-ray waves than SIMDs: 64^2 x (96+96) 0.80 -> 0.60 ms exact, 0.60 -> 0.45 tolerance — and the
     // tolerance mode at 96+96 (128^2: 0.63 -> 0.57 ms).  NOT the 128^2 exact launches (0.80 -> 0.88 at 96+96, 0.44 -> 0.49 at 48+48):
     // a decode step is ~4k MFMA clocks + ~1.5k VALU instructions of ISSUE, which ONE wave per SIMD already saturates; a second wave
@@ -2320,126 +1990,63 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     // SIMD (no spills: 64^2 x (96+96) 0.60 -> 0.50 ms) and stay the choice for <= 8192 rays only.
     const bool quad = pair && !(opts->flags & P3D_FLAG_PAIR16) &&
                       ((opts->flags & P3D_FLAG_QUAD8) || (long long)N * R <= 8192 || (fast && (nf == 96 || nf == 48)));
-    if (quad) {
-        if (p.tile_w > 0) { p.tiles_x = ray_tile_w / 4; p.tiles_per_img = (long long)p.tiles_x * (R / ray_tile_w / 2); }
-        else p.tiles_per_img = (R + 7) / 8;
+    dim3 grid, blk;
+    auto launch = [&](void (*kernel)(RenderParams)) {
+        hipError_t e = p3d_ensure_dynamic_lds(kernel, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(kernel, grid, blk, lds_bytes, st, p);
+        return p3d_check_launch();
+    };
+    int rc;
+    if (pair) {
+        const int rpw = quad ? 8 : 16;  // rays per wave: 32 / sample slots
+        if (p.tile_w > 0) { p.tiles_x = ray_tile_w / 4; p.tiles_per_img = (long long)p.tiles_x * (R / ray_tile_w / (rpw / 4)); }
+        else p.tiles_per_img = (R + rpw - 1) / rpw;
         p.ntiles = p.tiles_per_img * N;
-        nwaves = P3D_RENDER_WAVES;
-        for (;; nwaves >>= 1) {
-            lds_bytes = lds_fixed + (size_t)nwaves * p.lds_rows * 32;  // rows of 8 rays
-            if (2 * lds_bytes <= 160 * 1024) break;                    // two workgroups per CU
+        const int wgs = quad ? 2 : 1;  // workgroups per CU the LDS should fit: two for the four-slot form
+        for (nwaves = P3D_RENDER_WAVES;; nwaves >>= 1) {
+            lds_bytes = lds_fixed + (size_t)nwaves * p.lds_rows * rpw * 4;  // rows of rpw rays
+            if (wgs * lds_bytes <= 160 * 1024) break;
             if (nwaves == 1) { if (lds_bytes <= 160 * 1024) break; return P3D_E_RANGE; }
         }
-        dim3 grid4((unsigned)((p.ntiles + nwaves - 1) / nwaves)), blk4(64 * nwaves);
-        hipError_t e4 = hipSuccess;
-#define P3D_LAUNCH4F(NFV, FV)                                                                                        \
-    do {                                                                                                             \
-        e4 = p3d_ensure_dynamic_lds(k_render_quad<NFV, FV>, lds_bytes);                                              \
-        if (e4 == hipSuccess) hipLaunchKernelGGL((k_render_quad<NFV, FV>), grid4, blk4, lds_bytes, st, p);          \
-    } while (0)
-#define P3D_LAUNCH4(NFV) do { if (fast) P3D_LAUNCH4F(NFV, true); else P3D_LAUNCH4F(NFV, false); } while (0)
-#define P3D_LAUNCH4WO(NFV)                                                                                           \
-    do {                                                                                                             \
-        e4 = p3d_ensure_dynamic_lds(k_render_quad<NFV, true, true>, lds_bytes);                                      \
-        if (e4 == hipSuccess) hipLaunchKernelGGL((k_render_quad<NFV, true, true>), grid4, blk4, lds_bytes, st, p);  \
-    } while (0)
-        // P3D_FLAG_WEIGHTS_ONLY: honoured by the tolerance-mode quad kernels at 48 / 96 fine samples (what paste_front's occlusion pass runs)
-        const bool wo = fast && (opts->flags & P3D_FLAG_WEIGHTS_ONLY) != 0;
-#ifdef P3D_ONLY_NF
-        P3D_LAUNCH4(P3D_ONLY_NF);
-#else
-        if (wo && nf == 48) P3D_LAUNCH4WO(48);
-        else if (wo && nf == 96) P3D_LAUNCH4WO(96);
-        else if (nf == 48) P3D_LAUNCH4(48);
-        else if (nf == 64) P3D_LAUNCH4(64);
-        else if (nf == 96) P3D_LAUNCH4(96);
-        else P3D_LAUNCH4(0);
-#endif
-        if (e4 != hipSuccess) return (int)e4;
-        int rc4 = p3d_check_launch();
-        if (rc4) return rc4;
-        long long NR4 = (long long)N * R;
-        hipLaunchKernelGGL(k_render_finish, dim3((unsigned)((NR4 + 255) / 256)), dim3(256), 0, st, out_depth, NR4, p.gminmax,
-                           (float*)nullptr, p.per_view_clamp ? (long long)R : 0LL);
-        return p3d_check_launch();
-    }
-    if (pair) {
-        if (p.tile_w > 0) { p.tiles_x = ray_tile_w / 4; p.tiles_per_img = (long long)p.tiles_x * (R / ray_tile_w / 4); }
-        else p.tiles_per_img = (R + 15) / 16;
-        p.ntiles = p.tiles_per_img * N;
-        nwaves = P3D_RENDER_WAVES;
-        for (;; nwaves >>= 1) {
-            lds_bytes = lds_fixed + (size_t)nwaves * p.lds_rows * 128;
-            if (lds_bytes <= 160 * 1024) break;
-            if (nwaves == 1) return P3D_E_RANGE;
+        grid = dim3((unsigned)((p.ntiles + nwaves - 1) / nwaves));
+        blk = dim3(64 * nwaves);
+        // P3D_FLAG_WEIGHTS_ONLY: honoured by the tolerance-mode four-slot kernels at 48 / 96 fine samples (what paste_front's occlusion pass runs)
+        const bool wo = quad && fast && (opts->flags & P3D_FLAG_WEIGHTS_ONLY) != 0;
+        rc = p3d_with_nf(nf, [&](auto nfc) {
+            constexpr int NF = decltype(nfc)::value;
+            if constexpr (NF == 48 || NF == 96)
+                if (wo) return launch(k_render_slots<4, NF, true, true>);
+            if (quad) return launch(fast ? k_render_slots<4, NF, true> : k_render_slots<4, NF, false>);
+            return launch(fast ? k_render_slots<2, NF, true> : k_render_slots<2, NF, false>);
+        });
+    } else {
+        p.swz = 16;  // measured: 8..64 within 0.5 %, 1..4 and >= 256 about 1-3 % slower
+        p.blocked = 0;
+        {   // blocked tile order (k_render): whole 16 x 16-tile super-tiles per XCD run when the tile grid divides into them
+            static const int tile_order = getenv("P3D_TILE_ORDER") ? atoi(getenv("P3D_TILE_ORDER")) : 1;  // 0: row-major (A/B runs)
+            const long long tiles_y = p.tile_w > 0 ? p.tiles_per_img / p.tiles_x : 0;
+            // ... and into a multiple of 8 of them: 384^2 (18 super-tiles on 8 XCDs) loses 2-3 % to the imbalance, every shape with whole
+            // super-tiles per XCD is equal or up to 3 % better (profiles/r05_tile_order_shapes.json)
+            if (tile_order == 1 && p.tile_w > 0 && p.tiles_x % 16 == 0 && tiles_y % 16 == 0 && 256 % nwaves == 0 && (p.ntiles / 256) % 8 == 0) {
+                p.blocked = 1;
+                p.swz = 256 / nwaves;
+            }
         }
-        dim3 grid2((unsigned)((p.ntiles + nwaves - 1) / nwaves)), blk2(64 * nwaves);
-        hipError_t e2 = hipSuccess;
-#define P3D_LAUNCH2F(NFV, FV)                                                                                        \
-    do {                                                                                                             \
-        e2 = p3d_ensure_dynamic_lds(k_render_pair<NFV, FV>, lds_bytes);                                              \
-        if (e2 == hipSuccess) hipLaunchKernelGGL((k_render_pair<NFV, FV>), grid2, blk2, lds_bytes, st, p);          \
-    } while (0)
-#define P3D_LAUNCH2(NFV) do { if (fast) P3D_LAUNCH2F(NFV, true); else P3D_LAUNCH2F(NFV, false); } while (0)
-#ifdef P3D_ONLY_NF
-        P3D_LAUNCH2(P3D_ONLY_NF);
-#else
-        if (nf == 48) P3D_LAUNCH2(48);
-        else if (nf == 64) P3D_LAUNCH2(64);
-        else if (nf == 96) P3D_LAUNCH2(96);
-        else P3D_LAUNCH2(0);
-#endif
-        if (e2 != hipSuccess) return (int)e2;
-        int rc2 = p3d_check_launch();
-        if (rc2) return rc2;
-        long long NR2 = (long long)N * R;
-        hipLaunchKernelGGL(k_render_finish, dim3((unsigned)((NR2 + 255) / 256)), dim3(256), 0, st, out_depth, NR2, p.gminmax,
-                           (float*)nullptr, p.per_view_clamp ? (long long)R : 0LL);
-        return p3d_check_launch();
+        grid = dim3((unsigned)((p.ntiles + nwaves - 1) / nwaves));
+        blk = dim3(64 * nwaves);
+        rc = p3d_with_nf(nf, [&](auto nfc) {
+            constexpr int NF = decltype(nfc)::value;
+            auto mode = [&](auto fc) {
+                constexpr bool F = decltype(fc)::value;
+                if (dmp) return launch(k_render<NF, true, F, false>);
+                if (opts->flags & P3D_FLAG_NO_EARLY_OUT) return launch(k_render<NF, false, F, false>);
+                if (tcg) return launch(k_render<NF, false, F, true>);  // (NF == 96 only: the default TCG of that instantiation)
+                return launch(k_render<NF, false, F, true, false>);   // per-ray limits / disparity spacing at 96+96: the LDS-resident coarse column
+            };
+            return fast ? mode(std::true_type()) : mode(std::false_type());
+        });
     }
-    long long blocks = (p.ntiles + nwaves - 1) / nwaves;
-    p.swz = 16;  // measured: 8..64 within 0.5 %, 1..4 and >= 256 about 1-3 % slower
-    p.blocked = 0;
-    {   // blocked tile order (k_render): whole 16 x 16-tile super-tiles per XCD run when the tile grid divides into them
-        static const int tile_order = getenv("P3D_TILE_ORDER") ? atoi(getenv("P3D_TILE_ORDER")) : 1;  // 0: row-major (A/B runs)
-        const long long tiles_y = p.tile_w > 0 ? p.tiles_per_img / p.tiles_x : 0;
-        // ... and into a multiple of 8 of them: 384^2 (18 super-tiles on 8 XCDs) loses 2-3 % to the imbalance, every shape with whole
-        // super-tiles per XCD is equal or up to 3 % better (profiles/r05_tile_order_shapes.json)
-        if (tile_order == 1 && p.tile_w > 0 && p.tiles_x % 16 == 0 && tiles_y % 16 == 0 && 256 % nwaves == 0 && (p.ntiles / 256) % 8 == 0) {
-            p.blocked = 1;
-            p.swz = 256 / nwaves;
-        }
-    }
-    dim3 grid((unsigned)blocks), blk(64 * nwaves);
-    hipError_t e = hipSuccess;
-#define P3D_LAUNCH(NFV, DV, FV, EV)                                                                                  \
-    do {                                                                                                             \
-        e = p3d_ensure_dynamic_lds(k_render<NFV, DV, FV, EV>, lds_bytes);                                            \
-        if (e == hipSuccess) hipLaunchKernelGGL((k_render<NFV, DV, FV, EV>), grid, blk, lds_bytes, st, p);          \
-    } while (0)
-#define P3D_LAUNCH_NOTCG(NFV, FV)                                                                                   \
-    do {                                                                                                             \
-        e = p3d_ensure_dynamic_lds(k_render<NFV, false, FV, true, false>, lds_bytes);                                \
-        if (e == hipSuccess) hipLaunchKernelGGL((k_render<NFV, false, FV, true, false>), grid, blk, lds_bytes, st, p); \
-    } while (0)
-#define P3D_LAUNCH_F(NFV, FV)                                                                                        \
-    do {                                                                                                             \
-        if (dmp) P3D_LAUNCH(NFV, true, FV, false);                                                                   \
-        else if (opts->flags & P3D_FLAG_NO_EARLY_OUT) P3D_LAUNCH(NFV, false, FV, false);                             \
-        else if (tcg) P3D_LAUNCH(NFV, false, FV, true);  /* (NFV == 96 only: the default TCG of that instantiation) */ \
-        else P3D_LAUNCH_NOTCG(NFV, FV);  /* per-ray limits / disparity spacing at 96+96: the LDS-resident coarse column */ \
-    } while (0)
-#define P3D_LAUNCH_P(NFV) do { if (fast) P3D_LAUNCH_F(NFV, true); else P3D_LAUNCH_F(NFV, false); } while (0)
-#ifdef P3D_ONLY_NF  // development builds (tools/resource_usage.py -D P3D_ONLY_NF=48): compile ONE fine-depth capacity
-    P3D_LAUNCH_P(P3D_ONLY_NF);
-#else
-    if (nf == 48) P3D_LAUNCH_P(48);
-    else if (nf == 64) P3D_LAUNCH_P(64);
-    else if (nf == 96) P3D_LAUNCH_P(96);
-    else P3D_LAUNCH_P(0);
-#endif
-    if (e != hipSuccess) return (int)e;
-    int rc = p3d_check_launch();
     if (rc) return rc;
     long long NR = (long long)N * R;
     hipLaunchKernelGGL(k_render_finish, dim3((unsigned)((NR + 255) / 256)), dim3(256), 0, st, out_depth, NR, p.gminmax,

@@ -385,14 +385,10 @@ def render(planes_nhwc, rays_o, rays_d, jitter, u, mlp, opts, ray_tile_w=0, dump
         quad = pair and not (opts.flags & _lib.P3D_FLAG_PAIR16) and bool((opts.flags & _lib.P3D_FLAG_QUAD8) or N * R <= 8192 or
                                                                          ((opts.flags & _lib.P3D_FLAG_FAST_COLOR) and ((Sf == 96 and Sc <= 96) or Sf == 48)))
         kind = ("quad" if quad else "pair") if pair else None
-        if kind == "pair":  # 16 rays x 2 samples per wave-step
-            tiles = (R // 16) * N if tiled else -(-R // 16) * N
-            full = tiles * ((-(-Sc // 2) + -(-(Sc + Sf) // 2)) if Sf > 0 else -(-Sc // 2))
-        elif kind == "quad":  # 8 rays x 4 samples per wave-step
-            tiles = (R // 8) * N if tiled else -(-R // 8) * N
-            full = tiles * ((-(-Sc // 4) + -(-(Sc + Sf) // 4)) if Sf > 0 else -(-Sc // 4))
-        else:
-            full = tiles * (Sc + Sc + Sf if Sf > 0 else Sc)
+        slots = {"quad": 4, "pair": 2, None: 1}[kind]  # samples per wave-step, of 32 // slots rays each
+        rpw = 32 // slots
+        tiles = (R // rpw) * N if tiled else -(-R // rpw) * N
+        full = tiles * ((-(-Sc // slots) + -(-(Sc + Sf) // slots)) if Sf > 0 else -(-Sc // slots))
         stats.update(decode_steps=steps, decode_steps_full=full, small_launch_kernel=pair, small_launch_kind=kind)
     if weights_only:  # (feat / xyz may have been left unwritten)
         return None, depth, wsum, None

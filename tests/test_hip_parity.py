@@ -431,7 +431,7 @@ def test_render_random_configs_bit_exact(hip, oracle, seed, pair):
     kernels (the small-launch kernel these sizes would get, and the 32-rays-per-wave kernel forced).  Bit-exact."""
     c = _random_config(seed)
     mlp = hip_mlp(hip, c["raw"], c["lr_mul"])
-    # pair: small launches go to k_render_pair (16 rays x 2 samples per wave); not pair: the 32-rays-per-wave kernel
+    # pair: small launches go to k_render_slots (32 / SLOTS rays x SLOTS samples per wave); not pair: the 32-rays-per-wave kernel
     opts = hip.ops.make_opts(c["ro"], early_out=c["early_out"], small_launch_kernel=pair, **c["kw"])
     out = hip.ops.render(hip.ops.planes_to_nhwc(dev(c["planes"])), dev(c["o"]), dev(c["d"]), dev(c["jit"]), dev(c["u"]), mlp, opts,
                          ray_tile_w=c["tile_w"])
@@ -492,18 +492,20 @@ def test_fast_color_keeps_the_coarse_pass_exact_and_the_outputs_close(hip, oracl
     assert np.array_equal(hdm["depths_sorted"], np.take_along_axis(all_d, odm["perm"], axis=1))
     assert np.array_equal(hdm["tminmax"], odm["tminmax"])
     # production launches (no dumps, early-outs on) against the oracle: the 32-rays-per-wave kernel (small_launch_kernel=False —
-    # these fixtures are small launches) and the small-launch kernel (16 rays x 2 samples), which has its own tolerance variant
+    # these fixtures are small launches) and the small-launch kernel, which has its own tolerance variants: the size heuristic's
+    # choice, then both forms forced (8 rays x 4 samples, 16 rays x 2 samples; the heuristic picks the 4-slot one for all of these)
     prod = hip.ops.render(*args, hip.ops.make_opts(inp["ro"], fast_color=True, small_launch_kernel=False, **inp["kw"]))
-    st = {}
-    prod_pair = hip.ops.render(*args, hip.ops.make_opts(inp["ro"], fast_color=True, **inp["kw"]), stats=st)
-    assert st["small_launch_kernel"]
-    exact_pair = hip.ops.render(*args, hip.ops.make_opts(inp["ro"], **inp["kw"]))
-    assert not all(torch.equal(a, b) for a, b in zip(prod_pair, exact_pair)) or float(exact_pair[2].max()) == 0.0  # it really is another decoder
     R = inp["rays_o"].shape[0] * inp["rays_o"].shape[1]
-    for nm, a, b in zip(("feat", "depth", "wsum", "xyz"), prod_pair, ref[:4]):
-        err = np.abs(a.cpu().numpy() - b).reshape(R, -1).max(axis=1)
-        print(f"{name} fast-vs-oracle, small-launch kernel {nm}: max {err.max():.2e} median {np.median(err):.2e}")
-        assert np.median(err) <= 2e-6 and err.max() <= FAST_MAX[nm], (nm, float(err.max()), int((err > FAST_MAX[nm]).sum()))
+    for small in (True, "quad", "pair"):
+        st = {}
+        prod_pair = hip.ops.render(*args, hip.ops.make_opts(inp["ro"], fast_color=True, small_launch_kernel=small, **inp["kw"]), stats=st)
+        assert st["small_launch_kernel"] and (small is True or st["small_launch_kind"] == small), st
+        exact_pair = hip.ops.render(*args, hip.ops.make_opts(inp["ro"], small_launch_kernel=small, **inp["kw"]))
+        assert not all(torch.equal(a, b) for a, b in zip(prod_pair, exact_pair)) or float(exact_pair[2].max()) == 0.0  # it really is another decoder
+        for nm, a, b in zip(("feat", "depth", "wsum", "xyz"), prod_pair, ref[:4]):
+            err = np.abs(a.cpu().numpy() - b).reshape(R, -1).max(axis=1)
+            print(f"{name} fast-vs-oracle, small-launch kernel ({small}) {nm}: max {err.max():.2e} median {np.median(err):.2e}")
+            assert np.median(err) <= 2e-6 and err.max() <= FAST_MAX[nm], (small, nm, float(err.max()), int((err > FAST_MAX[nm]).sum()))
     # HARD bound (round 3): the exact mask guard (p3d_decode.hpp, P3D_FAST_MASK_BAND) makes the tolerance mode take the same
     # crop / cull decisions as the exact contract, so what is left is arithmetic round-off (two-term f16 products, hardware
     # exp2 / log2 / rcp, ray termination at Td < 2e-6): EVERY ray within FAST_MAX of the oracle, no allowance for flipped rays.
@@ -751,7 +753,7 @@ def test_staged_path_random_configs(hip, seed):
 def test_weights_only_launch_equals_the_full_launch(hip, Sc, Sf, res):
     """P3D_FLAG_WEIGHTS_ONLY (round 5): paste_front's occlusion pass reads `image_weights` of its second render and nothing else
     (training/triplane.py:565-578).  A ray's weights depend on depths and densities only, so the weights-only launch (tolerance mode,
-    small launches, 48 / 96 fine samples: k_render_quad<NF, true, true>) decodes no colours — and wsum / depth must be BIT-IDENTICAL to
+    small launches, 48 / 96 fine samples: k_render_slots<4, NF, true, true>) decodes no colours — and wsum / depth must be BIT-IDENTICAL to
     the full tolerance-mode launch's; where the library has no such instantiation (64 fine samples; a large launch; the exact mode) the
     hint is ignored and the same bits come from the full kernel."""
     ro = dict(T.RENDERING_KWARGS, depth_resolution=Sc, depth_resolution_importance=Sf)

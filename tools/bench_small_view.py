@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One small view (default 128^2 rays, 96+96 samples: what generate.py renders per view) on the three render kernels:
-the small-launch kernels (8 rays x 4 samples and 16 rays x 2 samples per wave) and the 32-rays-per-wave kernel."""
+both forms of the small-launch kernel k_render_slots (8 rays x 4 samples and 16 rays x 2 samples per wave) and the 32-rays-per-wave
+kernel k_render."""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Small-launch kernel (k_render_pair) at 128^2 rays: time and wave-level decode steps with the exact early-outs on / off, on the
+"""Small-launch kernel, 16 rays x 2 samples form (k_render_slots<2, ...>), at 128^2 rays: time and wave-level decode steps with the exact early-outs on / off, on the
 two bench scenes -> per-step cost and the fixed (non-decode) part of a wave."""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Run ON THE GPU BOX: counters of the pipeline's own renderer launch (128^2 rays x (96+96), k_render_quad, tolerance mode; and the
+# Run ON THE GPU BOX: counters of the pipeline's own renderer launch (128^2 rays x (96+96), k_render_slots<4, ...>, tolerance mode; and the
 # exact mode) — separate rocprofv3 --pmc passes, one counter group each, plus a kernel trace.  Condense: python tools/summarize_small_pmc.py <tag>
 set -u
 TAG=${1:-r04}

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The pipeline's own renderer launch in a loop — 128^2 rays x (96+96), surface scene, tolerance mode of the final pass unless
---exact, the kernel the host picks (k_render_quad) unless --kernel pair|classic — for rocprofv3 passes (tools/pmc_small_view.sh)."""
+--exact, the kernel the host picks (k_render_slots<4, ...>) unless --kernel pair|classic — for rocprofv3 passes (tools/pmc_small_view.sh)."""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
