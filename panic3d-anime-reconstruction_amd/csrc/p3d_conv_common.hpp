@@ -6,15 +6,13 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "../../include/panic3d_hip.h"
+#include "p3d_conv_plan.hpp"
 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define DEV __device__ __forceinline__
 
-#define CONV_TH 8
-#define CONV_TW 16
 #define XS_ROW (CONV_TW + 2)
 #define XS_PLANE ((CONV_TH + 2) * XS_ROW)
 // a K chunk = 8 input channels (72 k values for 3x3, 8 for 1x1)
@@ -90,7 +88,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // Out of domain: a scaled operand beyond the f16 range (|s*x| > 65504 / 16 = 4094, or NaN) is clamped to +-65504 — finite, wrong —
 // and the CALLER's flag word (ConvParams::sat, the `saturated` argument of p3d_modconv2d_f16x2mma_f32) is OR-ed with 1: no state
 // lives in the library.
-#define WX_TW 32
 #define WX_ROW (WX_TW + 2)                         // patch columns = LDS row pitch (px)
 
 #define U3_WB (2 * 9 * 64 * 16)                    // one buffer of weights: 18 432
@@ -155,16 +152,8 @@ static inline int chk_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? P3D_OK : (int)e;
 }
-// The kernel-selection switches of the environment (A/B runs) are read ONCE per process: what p3d_modconv2d_workspace_bytes
-// answered for a shape stays the size the launch of that shape needs (a caller may cache the query).
-// narrowest map the pipelined plain 3x3 kernel (k_modconv_w3, a 32-column tile) takes; P3D_W3_MIN_W in the environment: A/B runs
-#ifndef P3D_W3_MIN_W
-#define P3D_W3_MIN_W 32
-#endif
-static inline int p3d_w3_min_w() { static const int v = getenv("P3D_W3_MIN_W") ? atoi(getenv("P3D_W3_MIN_W")) : P3D_W3_MIN_W; return v; }
-static inline bool p3d_env_no_w3() { static const bool v = getenv("P3D_NO_W3") != nullptr; return v; }
-void p3d_launch_conv_plain(const ConvParams& p, hipStream_t st);            // p3d_conv_plain.hip
-void p3d_launch_conv_up(const ConvParams& p, int kind, hipStream_t st);     // p3d_conv_up.hip
-void p3d_launch_fir_pass(const FirParams& q, char* yimg, long long lo_off, unsigned int* sat, hipStream_t st);  // p3d_fir.hip
-int p3d_up4_shape(int N, int O, int H, int W);                               // p3d_conv_up4.hip
-int p3d_up4_launch(const ConvParams& p, int rpw, hipStream_t st);
+// the launchers: each launches the kernel a plan names (p3d_conv_plan.hpp) and decides nothing
+void p3d_launch_conv_plain(const ConvParams& p, ConvKernel k, ConvGrid g, hipStream_t st);  // p3d_conv_plain.hip
+void p3d_launch_conv_up(const ConvParams& p, ConvKernel k, ConvGrid g, hipStream_t st);     // p3d_conv_up.hip
+void p3d_launch_conv_up4(const ConvParams& p, ConvKernel k, ConvGrid g, hipStream_t st);    // p3d_conv_up4.hip
+void p3d_launch_fir_pass(const FirParams& q, ConvTail t, ConvGrid g, char* yimg, long long lo_off, unsigned int* sat, hipStream_t st);  // p3d_fir.hip

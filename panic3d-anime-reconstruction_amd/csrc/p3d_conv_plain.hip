@@ -621,26 +621,19 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w3(ConvParams p) {
 
 // Tile variants measured on MI355X and rejected (with the first version of these kernels): 128-channel output tiles (two A tiles
 // per wave; 256->256 @256^2: 53 vs 66 TF: fewer, fatter workgroups) and 16-row pixel tiles (58.7 vs 66 TF).
-void p3d_launch_conv_plain(const ConvParams& p, hipStream_t st) {
-    const bool k3 = p.ks == 3;
-    dim3 grid(((p.GW + CONV_TW - 1) / CONV_TW) * ((p.GH + CONV_TH - 1) / CONV_TH), (p.O + 63) / 64, p.N * p.ksplit);
-    if (p.wh && p.wsplit && k3 && p.GW >= p3d_w3_min_w()) {  // the wide tile (the split-K factor was chosen for it: modconv_impl)
-        dim3 gw(((p.GW + WX_TW - 1) / WX_TW) * ((p.GH + CONV_TH - 1) / CONV_TH), (p.O + 63) / 64, p.N * p.ksplit);
-        if (p.ximg && p.O % 64 == 0 && !p3d_env_no_w3()) {
-            if (p.rgbp) hipLaunchKernelGGL(k_modconv_w3<true>, gw, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(k_modconv_w3<false>, gw, dim3(256), 0, st, p);
-        }
-        else if (p.ximg) hipLaunchKernelGGL(k_modconv_w2<true>, gw, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_modconv_w2<false>, gw, dim3(256), 0, st, p);
-        return;
-    }
-    if (k3) {
-        if (p.wh && p.wsplit) hipLaunchKernelGGL((k_modconv_h<0, true>), grid, dim3(256), 0, st, p);
-        else if (p.wh) hipLaunchKernelGGL((k_modconv_h<0, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_modconv<0>), grid, dim3(256), 0, st, p);
-    } else {
-        if (p.wh && p.wsplit) hipLaunchKernelGGL((k_modconv_h<1, true>), grid, dim3(256), 0, st, p);
-        else if (p.wh) hipLaunchKernelGGL((k_modconv_h<1, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_modconv<1>), grid, dim3(256), 0, st, p);
+void p3d_launch_conv_plain(const ConvParams& p, ConvKernel k, ConvGrid g, hipStream_t st) {
+    const dim3 grid(g.x, g.y, g.z);
+    switch (k) {
+    case ConvKernel::W3_RGB: hipLaunchKernelGGL(k_modconv_w3<true>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::W3: hipLaunchKernelGGL(k_modconv_w3<false>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::W2_IMG: hipLaunchKernelGGL(k_modconv_w2<true>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::W2: hipLaunchKernelGGL(k_modconv_w2<false>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::H_3_X2: hipLaunchKernelGGL((k_modconv_h<0, true>), grid, dim3(256), 0, st, p); break;
+    case ConvKernel::H_3: hipLaunchKernelGGL((k_modconv_h<0, false>), grid, dim3(256), 0, st, p); break;
+    case ConvKernel::MODCONV_3: hipLaunchKernelGGL((k_modconv<0>), grid, dim3(256), 0, st, p); break;
+    case ConvKernel::H_1_X2: hipLaunchKernelGGL((k_modconv_h<1, true>), grid, dim3(256), 0, st, p); break;
+    case ConvKernel::H_1: hipLaunchKernelGGL((k_modconv_h<1, false>), grid, dim3(256), 0, st, p); break;
+    case ConvKernel::MODCONV_1: hipLaunchKernelGGL((k_modconv<1>), grid, dim3(256), 0, st, p); break;
+    default: break;
     }
 }

@@ -786,28 +786,17 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
     }
 }
 
-// kind: 0 = the register-staged kernels (by operand mode), 1 = k_modconv_up3<false> (raw intermediate / split-K partials),
-// 2 = k_modconv_up3<true> (FIR pass and epilogue inside; p.H, p.W: the layer's input map)
-void p3d_launch_conv_up(const ConvParams& p, int kind, hipStream_t st) {
-    if (kind == 2) {
-        dim3 gf(((2 * p.W + 59) / 60) * ((2 * p.H + 11) / 12), p.O / 32, p.N);
-        hipLaunchKernelGGL(k_modconv_up3<true>, gf, dim3(256), 0, st, p);
-    } else if (kind == 1) {
-        dim3 g3(((p.GW + WX_TW - 1) / WX_TW) * ((p.GH + 7) / 8), p.O / 32, p.N * p.ksplit);
-        // k_modconv_up5 (one workgroup per CU, deep prefetch) while the launch leaves the chip under-filled anyway: up to two workgroups
-        // per CU in k_modconv_up3's terms; P3D_UP5=0 / 1 in the environment: never / always (tests, A/B runs)
-        const char* e5 = getenv("P3D_UP5");  // (read per call: tests switch it)
-        const int up5 = e5 ? atoi(e5) : -1;
-        const long long wgs = (long long)g3.x * g3.y * g3.z;
-        // ... and a K slice is at least eight chunks: the deep ring's prologue requests three patches and two weight chunks before the first
-        // MFMA — on the four-chunk slices of the 16^2 -> 32^2 layer it costs more than it hides (23.7 against 19.5 us, same lease);
-        // 512 -> 512 @32^2 -> 64^2: 41.5 -> 30.5 us, 512 -> 256 @64^2 -> 128^2: 45.2 -> 42.8
-        if (up5 != 0 && p.O % 32 == 0 && (up5 == 1 || (wgs <= 640 && p.I / p.ksplit >= 128))) hipLaunchKernelGGL(k_modconv_up5, dim3((unsigned)wgs), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL(k_modconv_up3<false>, g3, dim3(256), 0, st, p);
-    } else {
-        dim3 grid(((p.GW + CONV_TW - 1) / CONV_TW) * ((p.GH + CONV_TH - 1) / CONV_TH), (p.O + 63) / 64, p.N * p.ksplit);
-        if (p.wh && p.wsplit) hipLaunchKernelGGL(k_modconv_up_h<true>, grid, dim3(256), 0, st, p);
-        else if (p.wh) hipLaunchKernelGGL(k_modconv_up_h<false>, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_modconv_up, grid, dim3(256), 0, st, p);
+// k_modconv_up3<true>: the FIR pass and the epilogue inside (p.H, p.W: the layer's input map); the others store the raw
+// intermediate / split-K partials
+void p3d_launch_conv_up(const ConvParams& p, ConvKernel k, ConvGrid g, hipStream_t st) {
+    const dim3 grid(g.x, g.y, g.z);
+    switch (k) {
+    case ConvKernel::UP3_FUSED: hipLaunchKernelGGL(k_modconv_up3<true>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::UP5: hipLaunchKernelGGL(k_modconv_up5, grid, dim3(512), 0, st, p); break;
+    case ConvKernel::UP3: hipLaunchKernelGGL(k_modconv_up3<false>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::UP_H_X2: hipLaunchKernelGGL(k_modconv_up_h<true>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::UP_H: hipLaunchKernelGGL(k_modconv_up_h<false>, grid, dim3(256), 0, st, p); break;
+    case ConvKernel::UP: hipLaunchKernelGGL(k_modconv_up, grid, dim3(256), 0, st, p); break;
+    default: break;
     }
 }

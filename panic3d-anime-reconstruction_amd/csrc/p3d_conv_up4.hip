@@ -397,15 +397,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
 
 }  // namespace
 
-// workgroups of a launch whose tiles hold `rows` grid rows: (spatial tiles, channel tiles, samples)
-static dim3 up4_grid(const ConvParams& p, int rows) {
-    const int orows = 2 * rows - 4;
-    return dim3((unsigned)(((2 * p.W + 59) / 60) * ((2 * p.H + orows - 1) / orows)), (unsigned)(p.O / 32), (unsigned)p.N);
-}
-
-// The launch shape the host picks: 2 = eight waves x 2 rows (16 x 32 grid points, one workgroup per CU: 1.22 x instead of 1.42 x the
-// MFMA work) once that tiling alone gives every CU two rounds of workgroups; 0 = four waves x 2 rows (8 x 32 grid points, 78 KB of
-// LDS: two workgroups per CU) below that.  Measured (tools/up4_ab.py, us, image in / image out, batch 1; r05 = k_modconv_up3 + FIR pass):
+// The launch shapes the plan picks from (p3d_conv_plan.hpp): shape 2 (UP4_16) = eight waves x 2 rows (16 x 32 grid points, one
+// workgroup per CU: 1.22 x instead of 1.42 x the MFMA work) once that tiling alone gives every CU two rounds of workgroups; shape 0
+// (UP4_8) = four waves x 2 rows (8 x 32 grid points, 78 KB of LDS: two workgroups per CU) below that.  Measured (tools/up4_ab.py, us, image in / image out, batch 1; r05 = k_modconv_up3 + FIR pass):
 //   256 -> 128 @256^2 -> 512^2 (684 / 1548 workgroups):  r05 238   shape 2 191   shape 0 206
 //   256 -> 128 @128^2 -> 256^2 (200 / 440):              r05 68    shape 2 65    shape 0 64
 //   512 -> 256 @ 64^2 -> 128^2 (120 / 264):              r05 64    shape 2 84    shape 0 101   (the chip is underfilled: split-K wins)
@@ -414,19 +408,9 @@ static dim3 up4_grid(const ConvParams& p, int rows) {
 // four-wave four-row shape — the 16 x 32 tile on ONE wave per SIMD, 256 accumulator + 256 other registers, 108 MFMAs per chunk and
 // 0.35 instead of 0.55 LDS reads per MFMA: bit-identical and slower everywhere (256^2 -> 512^2: 209 us against 197; 32 -> 256: 73 / 65;
 // the small maps 84-113 against 52-88): without a second wave on the SIMD every LDS round trip of the loop and of the filter is exposed.
-// P3D_UP4_RPW = 0 / 2 in the environment forces a shape (A/B runs, tests).
-int p3d_up4_shape(int N, int O, int H, int W) {
-    const char* e = getenv("P3D_UP4_RPW");
-    if (e && (atoi(e) == 0 || atoi(e) == 2)) return atoi(e);
-    const long long wg16 = (long long)((2 * W + 59) / 60) * ((2 * H + 27) / 28) * (O / 32) * N;
-    return wg16 >= 512 ? 2 : 0;
-}
-
 // up = 2, image-fed (p.ximg), unsplit, I % 16 == 0, O % 32 == 0; writes p.yimg (activation image, needs p.ystyles) or p.y (fp32 [N][O][2H][2W])
-int p3d_up4_launch(const ConvParams& p0, int shape, hipStream_t st) {
-    const ConvParams& p = p0;
-    if (shape == 2) hipLaunchKernelGGL((k_modconv_up4<8, 2, 3>), up4_grid(p, 16), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((k_modconv_up4<4, 2, 2>), up4_grid(p, 8), dim3(256), 0, st, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? P3D_OK : (int)e;
+void p3d_launch_conv_up4(const ConvParams& p, ConvKernel k, ConvGrid g, hipStream_t st) {
+    const dim3 grid(g.x, g.y, g.z);
+    if (k == ConvKernel::UP4_16) hipLaunchKernelGGL((k_modconv_up4<8, 2, 3>), grid, dim3(512), 0, st, p);
+    else if (k == ConvKernel::UP4_8) hipLaunchKernelGGL((k_modconv_up4<4, 2, 2>), grid, dim3(256), 0, st, p);
 }

@@ -562,26 +562,17 @@ __global__ __launch_bounds__(256, 2) void k_fir4x4_img2(FirParams p, char* __res
     if (bad && sat) atomicOr(sat, 1u);
 }
 
-// the FIR pass of an up-sampling layer (modconv_impl): q describes the (2H+1) x (2W+1) intermediate; yimg: write the next layer's image
-void p3d_launch_fir_pass(const FirParams& q, char* yimg, long long lo_off, unsigned int* sat, hipStream_t st) {
-    dim3 grid(((q.OW + 31) / 32) * ((q.OH + 31) / 32), (unsigned)q.NC);
-    if (yimg) {
-        dim3 gi(grid.x, (unsigned)(q.NC / 8));
-        const bool rows_aligned = (q.pitch & 3) == 0 && q.xoff == q.padx0 && (((uintptr_t)q.x | (uintptr_t)(q.slice * 4)) & 15) == 0;
-        // two channels per stage: 125 VGPRs, four waves per SIMD (four per stage: 195, two; measured 2-5 % slower)
-        // k_fir4x4_img2 where k_fir4x4_img's 32 x 32 tiles are too few workgroups for the chip (512 channels at 32^2: 64 of them, 17.6 us;
-        // 8-row tiles: 256, 13.8 us).  On the larger maps the older kernel — which requests its next stage while it filters — stays ahead
-        // despite its bank conflicts (64^2: 13.3 against 15.9 us, 128^2: 20.2 against 27.8 - 30.9: measured, profiles/r06_notes.txt).
-        // P3D_FIR_IMG2=0 / 8 / 32 in the environment: never / always with that tile height (tests, A/B runs).
-        const char* e2 = getenv("P3D_FIR_IMG2");
-        const int force = e2 ? atoi(e2) : -1;
-        const bool can2 = rows_aligned && q.xoff == 1 && q.pady0 == 1 && q.fh == 4 && q.fw == 4 && force != 0;
-        if (can2 && (force == 8 || force == 32 || (long long)gi.x * gi.y < 128)) {
-            if (force == 32) hipLaunchKernelGGL((k_fir4x4_img2<32>), dim3((unsigned)(((q.OW + 63) / 64) * ((q.OH + 31) / 32)), (unsigned)(q.NC / 8)), dim3(256), 0, st, q, yimg, lo_off, sat);
-            else hipLaunchKernelGGL((k_fir4x4_img2<8>), dim3((unsigned)(((q.OW + 63) / 64) * ((q.OH + 7) / 8)), (unsigned)(q.NC / 8)), dim3(256), 0, st, q, yimg, lo_off, sat);
-        } else if (rows_aligned) hipLaunchKernelGGL((k_fir4x4_img<true, 2, 3>), gi, dim3(256), 0, st, q, yimg, lo_off, sat);
-        else hipLaunchKernelGGL((k_fir4x4_img<false, 4, 2>), gi, dim3(256), 0, st, q, yimg, lo_off, sat);
-    } else hipLaunchKernelGGL(k_fir4x4_tiled, grid, dim3(256), 0, st, q);
+// the FIR pass of an up-sampling layer (modconv_impl): q describes the (2H+1) x (2W+1) intermediate; yimg: the next layer's image
+void p3d_launch_fir_pass(const FirParams& q, ConvTail t, ConvGrid g, char* yimg, long long lo_off, unsigned int* sat, hipStream_t st) {
+    const dim3 grid(g.x, g.y, g.z);
+    switch (t) {
+    case ConvTail::FIR_IMG2_32: hipLaunchKernelGGL((k_fir4x4_img2<32>), grid, dim3(256), 0, st, q, yimg, lo_off, sat); break;
+    case ConvTail::FIR_IMG2_8: hipLaunchKernelGGL((k_fir4x4_img2<8>), grid, dim3(256), 0, st, q, yimg, lo_off, sat); break;
+    case ConvTail::FIR_IMG_ALIGNED: hipLaunchKernelGGL((k_fir4x4_img<true, 2, 3>), grid, dim3(256), 0, st, q, yimg, lo_off, sat); break;
+    case ConvTail::FIR_IMG: hipLaunchKernelGGL((k_fir4x4_img<false, 4, 2>), grid, dim3(256), 0, st, q, yimg, lo_off, sat); break;
+    case ConvTail::FIR_TILED: hipLaunchKernelGGL(k_fir4x4_tiled, grid, dim3(256), 0, st, q); break;
+    default: break;
+    }
 }
 
 extern "C" {

@@ -213,145 +213,45 @@ __global__ void k_demod_plan(const float* __restrict__ w2, const float* __restri
     if (lane == 0) d[t[2] + local] = 1.0f / __builtin_sqrtf(acc + 1e-8f);
 }
 
-#ifndef P3D_KSPLIT_TARGET
-#define P3D_KSPLIT_TARGET 256  // workgroups a launch is split towards.  Batch-1 backbone, ms: 64 -> 1.31, 128 -> 1.15, 256 -> 1.08, 512 (rounds 1-2) -> 1.15, 1024 -> 1.36 (profiles/history/r03_notes.txt)
-#endif
-// split-K factor: small feature maps (4^2..64^2) give too few workgroups for 256 CUs; split the K loop until ~512
-static int ksplit_target_image() {  // the image-fed kernels (k_modconv_w3 / k_modconv_up3); P3D_KSPLIT_TARGET_IMG in the environment: A/B runs
-    static const int v = getenv("P3D_KSPLIT_TARGET_IMG") ? atoi(getenv("P3D_KSPLIT_TARGET_IMG")) : P3D_KSPLIT_TARGET;
-    return v;
-}
-static int choose_ksplit(int N, int I, int O, int GH, int GW, int tw = CONV_TW) {
-    long long wgs = (long long)((GW + tw - 1) / tw) * ((GH + CONV_TH - 1) / CONV_TH) * ((O + 63) / 64) * N;
-    int ks = 1;
-    if (tw == WX_TW) {
-        while (ks < 64 && wgs * ks < ksplit_target_image() && I / (ks * 2) >= 8) ks *= 2;
-        return ks;
-    }
-    // down to ONE 8-channel chunk per workgroup: at batch 1 the 4^2..16^2 layers are a weight stream (9.4 MB for 512 -> 512 x 3x3)
-    // that 8..16 workgroups cannot pull in; measured at batch 1: b4.conv1 36 -> see profiles/history/r02_notes.txt
-    while (ks < 64 && wgs * ks < P3D_KSPLIT_TARGET && I / (ks * 2) >= 8) ks *= 2;
-    return ks;
-}
-
-// k_modconv_up3 (image-fed, DMA-pipelined transposed convolution): two-term operands, 16-channel chunks, 32-channel output tiles,
-// every map from 4^2 up: below W = 32 its 32-column tile is mostly empty, but the 4^2 .. 16^2 layers are latency, not arithmetic, and
-// the pipelined kernel (+ the 5 us conversion pass of its input) still beats k_modconv_up_h there (measured, batch-1 backbone as a
-// hipGraph replay: W >= 32 only 0.709 ms, >= 16 0.688, >= 8 0.680-0.689, >= 4 0.689; W = 32: 65.2 -> 47.7 + 4.8 us at 512 -> 512)
-#ifndef P3D_UP3_MIN_W
-#define P3D_UP3_MIN_W 4
-#endif
-static int up3_min_w() {  // (P3D_UP3_MIN_W in the environment: A/B runs)
-    static const int v = getenv("P3D_UP3_MIN_W") ? atoi(getenv("P3D_UP3_MIN_W")) : P3D_UP3_MIN_W;
-    return v;
-}
-// The kernel-selection switches of the environment (A/B runs) are read ONCE per process: what p3d_modconv2d_workspace_bytes
-// answered for a shape stays the size the launch of that shape needs (a caller may cache the query).
-static bool env_no_up3() { static const bool v = getenv("P3D_NO_UP3") != nullptr; return v; }
-static bool up3_applies(int I, int O, int W) { return I % 16 == 0 && O % 32 == 0 && W >= up3_min_w() && !env_no_up3(); }
-// k_modconv_up4 (p3d_conv_up4.hip)
-// P3D_UP4=0 in the environment: the round-5 kernels (k_modconv_up3 + FIR pass) for every layer; P3D_UP4_MIN_WGS / P3D_UP4_MIN_I: the
-// launch size (workgroups of the 8-row tiling) and K depth from which the one-launch form is taken — defaults 384 and 64: measured
-// (p3d_conv_up4.hip, above p3d_up4_shape) it wins from the 128^2 -> 256^2 layer of the backbone up, loses on underfilled launches
-// (split-K fills the chip) and on two-chunk K loops.  Read per call (tests switch them), like P3D_UP3_FUSED.
-static bool up4_applies(int N, int I, int O, int H, int W) {
-    const char* e = getenv("P3D_UP4");
-    if (e && atoi(e) == 0) return false;
-    const char* m = getenv("P3D_UP4_MIN_WGS");
-    const char* mi = getenv("P3D_UP4_MIN_I");
-    const long long min_wgs = m ? atoll(m) : 384;
-    const long long wgs = (long long)((2 * W + 59) / 60) * ((2 * H + 11) / 12) * (O / 32) * N;
-    return wgs >= min_wgs && I >= (mi ? atoi(mi) : 64);
-}
-static int choose_ksplit_up3(int N, int I, int O, int H, int W) {
-    long long wgs = (long long)((W + 1 + WX_TW - 1) / WX_TW) * ((H + 1 + 7) / 8) * (O / 32) * N;
-    static const int target_up = getenv("P3D_KSPLIT_TARGET_UP") ? atoi(getenv("P3D_KSPLIT_TARGET_UP")) : 0;  // (A/B runs; 0: the image kernels' target)
-    const int target = target_up > 0 ? target_up : ksplit_target_image();
-    int ks = 1;
-    while (ks < 64 && wgs * ks < target && I / (ks * 2) >= 16) ks *= 2;
-    return ks;
-}
-
-static bool rgb_fusable(int N, int I, int O, int H, int W, int rgbo) {
-    return rgbo >= 1 && rgbo <= 4 && I % 16 == 0 && O % 64 == 0 && W >= WX_TW && !p3d_env_no_w3() && !getenv("P3D_NO_RGB_FUSE") &&
-           choose_ksplit(N, I, O, H, W, WX_TW) == 1;
-}
-
 extern "C" {
 
 int p3d_conv_fuses_torgb(int N, int I, int O, int H, int W, int rgb_channels) {
     if (N <= 0 || I <= 0 || O <= 0 || H <= 0 || W <= 0) return 0;
-    return rgb_fusable(N, I, O, H, W, rgb_channels) ? 1 : 0;
+    return conv_rgb_fusable(N, I, O, H, W, rgb_channels) ? 1 : 0;
 }
 size_t p3d_torgb_partial_bytes(int N, int O, int H, int W, int rgb_channels) {
     return (size_t)(O / 64) * N * rgb_channels * H * W * 4;
 }
-
-size_t p3d_modconv2d_workspace_bytes(int N, int I, int O, int H, int W, int up) {
-    size_t b = (size_t)N * O * 4 + 256;  // demodulation coefficients
-    size_t out_elems = (up == 2) ? (size_t)N * O * (2 * H + 1) * (2 * W + 4) : (size_t)N * O * H * W;  // (up = 2: the intermediate's row pitch)
-    if (up == 2) b += out_elems * 4;  // transposed-conv intermediate
-    int ks = choose_ksplit(N, I, O, up == 2 ? H + 1 : H, up == 2 ? W + 1 : W);
-    if (up == 1 && W >= p3d_w3_min_w()) {  // the wide tile of the two-term kernel may split deeper
-        const int kw = choose_ksplit(N, I, O, H, W, WX_TW);
-        ks = kw > ks ? kw : ks;
-    }
-    if (ks > 1) b += (size_t)ks * out_elems * 4;  // split-K partial sums
-    if (up == 1 && W >= p3d_w3_min_w() && I % 16 == 0 && O % 64 == 0) b += (size_t)N * I * H * W * 4 + 256;  // the activation image an fp32 input is turned into (k_modconv_w3)
-    if (up == 2 && up3_applies(I, O, W)) {  // k_modconv_up3: its own split-K depth, and the activation image of an fp32 input
-        const int k3 = choose_ksplit_up3(N, I, O, H, W);
-        if (k3 > ks) b += (size_t)(k3 - (ks > 1 ? ks : 0)) * out_elems * 4;
-        b += (size_t)N * I * H * W * 4 + 256;
-    }
-    return b + 256;
-}
-
-// the layout of the two-term weight copy the dispatch of a 3x3 layer can consume (W: the input map's width): the image layouts where
-// the layer runs on the pipelined kernels whatever its batch size and split-K depth, OIK elsewhere; P3D_WLAYOUT=0 in the environment
-// (read once): OIK everywhere (A/B runs)
-int p3d_conv_weight_layout(int I, int O, int W, int up) {
-    static const bool off = getenv("P3D_WLAYOUT") && atoi(getenv("P3D_WLAYOUT")) == 0;
-    if (off || I <= 0 || O <= 0 || W <= 0 || I % 16 != 0) return P3D_WLAYOUT_OIK;
-    if (up == 1 && O % 64 == 0 && W >= p3d_w3_min_w() && !p3d_env_no_w3()) return P3D_WLAYOUT_PLAIN;
-    if (up == 2 && up3_applies(I, O, W)) return P3D_WLAYOUT_UP;
-    return P3D_WLAYOUT_OIK;
-}
-
+size_t p3d_modconv2d_workspace_bytes(int N, int I, int O, int H, int W, int up) { return p3d_conv_workspace_bytes(N, I, O, H, W, up); }
+int p3d_conv_weight_layout(int I, int O, int W, int up) { return conv_weight_layout(I, O, W, up); }
 // the rule by which an image-consuming layer is accepted (p3d_conv_args.x_img): exported so that a binding cannot drift from it
-int p3d_conv_takes_image(int I, int O, int W, int up) {
-    if (I <= 0 || O <= 0 || W <= 0 || I % 16 != 0) return 0;
-    if (up == 1) return W >= p3d_w3_min_w() ? 1 : 0;
-    if (up == 2) return up3_applies(I, O, W) ? 1 : 0;
-    return 0;
-}
+int p3d_conv_takes_image(int I, int O, int W, int up) { return conv_takes_image(I, O, W, up) ? 1 : 0; }
+
+}  // extern "C"
 
 // the block's ToRGB layer riding on its conv1 launch (p3d_conv_args.rgb_*)
 struct RgbFuse { const float* w; const float* styles; float* partial; int channels; };
 
-// The launch that takes the ToRGB layer along: the pipelined plain 3x3 kernel, unsplit (the activation image as input is the caller's
-// business: it is asked for p3d_conv_takes_image as well)
-static bool rgb_fusable(int N, int I, int O, int H, int W, int rgbo);
-
 static int modconv_impl(const float* x, int N, int I, int H, int W, const float* w, const void* wh, int wsplit, int O, int ks,
                         const float* styles, int demodulate, const float* dcoef_in, const float* noise, int noise_per_sample, const float* bias,
                         int up, int act, float alpha, float gain, float clamp, const float* fir, float* y, void* workspace,
-                        size_t workspace_bytes, void* stream, unsigned int* sat = nullptr, const void* ximg = nullptr,
-                        void* yimg = nullptr, const float* ystyles = nullptr, const RgbFuse* rgb = nullptr, int wlayout = P3D_WLAYOUT_OIK) {
+                        size_t workspace_bytes, void* stream, unsigned int* sat, const void* ximg, void* yimg, const float* ystyles,
+                        const RgbFuse* rgb, int wlayout) {
     if (rgb && !rgb->partial) rgb = nullptr;
     // a weight copy in one of the image layouts: only for a layer that runs on the kernel whose LDS image it is (an fp32 input is
     // turned into an activation image first, so the pipelined kernels take those layers whichever way their input arrives)
-    if (wlayout != P3D_WLAYOUT_OIK && (!wh || !wsplit || ks != 3 || wlayout != p3d_conv_weight_layout(I, O, W, up))) return P3D_E_RANGE;
+    if (wlayout != P3D_WLAYOUT_OIK && (!wh || !wsplit || ks != 3 || wlayout != conv_weight_layout(I, O, W, up))) return P3D_E_RANGE;
     if ((!x && !ximg) || !w || (!styles && !ximg) || (!y && !yimg && !rgb) || (y && yimg && up == 2) || (!y && up == 1 && !rgb) || !workspace || N <= 0 ||
         I <= 0 || O <= 0 || H <= 0 || W <= 0)
         return P3D_E_ARG;
     if (rgb) {
         if (!rgb->w || !rgb->styles) return P3D_E_ARG;
-        if (up != 1 || ks != 3 || !ximg || !wh || !wsplit || !rgb_fusable(N, I, O, H, W, rgb->channels)) return P3D_E_RANGE;
+        if (up != 1 || ks != 3 || !ximg || !wh || !wsplit || !conv_rgb_fusable(N, I, O, H, W, rgb->channels)) return P3D_E_RANGE;
     }
     if (ximg) {  // an image input (already modulated by its producer): the pipelined two-term kernels; demodulation must be precomputed
         if (!wh || !wsplit || (demodulate && !dcoef_in)) return P3D_E_ARG;
         if (ks != 3 || I % 16 != 0 || ((uintptr_t)ximg & 15)) return P3D_E_RANGE;
-        if (up == 1 ? W < p3d_w3_min_w() : !up3_applies(I, O, W)) return P3D_E_RANGE;  // (an up-sampling layer reads images only through k_modconv_up3)
+        if (up == 1 ? !conv_w_wide(W) : !conv_up3_applies(I, O, W)) return P3D_E_RANGE;  // (an up-sampling layer reads images only through k_modconv_up3)
     }
     if (yimg) {      // an image output for a consumer with styles ystyles [N][O]: up = 2: written by the FIR pass INSTEAD of y; up = 1: next to y
         if (!ystyles) return P3D_E_ARG;
@@ -361,124 +261,109 @@ static int modconv_impl(const float* x, int N, int I, int H, int W, const float*
     if ((long long)I * H * W * 4 >= (1ll << 31) || (long long)O * I * ks * ks * 4 >= (1ll << 31)) return P3D_E_RANGE;
     if (!((ks == 3 && (up == 1 || up == 2)) || (ks == 1 && up == 1))) return P3D_E_RANGE;
     if (up == 2 && !fir) return P3D_E_ARG;
-    if (workspace_bytes < p3d_modconv2d_workspace_bytes(N, I, O, H, W, up)) return P3D_E_WORKSPACE;
-    // the carve-up below rounds its regions to 256 bytes from the BASE: the budget of the query holds for a 256-byte aligned base
-    // (hipMalloc and torch allocations are); anything else is refused rather than written past
+    if (workspace_bytes < p3d_conv_workspace_bytes(N, I, O, H, W, up)) return P3D_E_WORKSPACE;
+    // the plan's regions start 256-byte aligned from the BASE: the budget of the query holds for a 256-byte aligned base (hipMalloc and
+    // torch allocations are); anything else is refused rather than written past
     if ((uintptr_t)workspace & 255) return P3D_E_RANGE;
+    const int mma = !wh ? P3D_CONV_MMA_F32 : wsplit ? P3D_CONV_MMA_F16X2 : P3D_CONV_MMA_F16;
+    const ConvPlan pl = p3d_conv_plan({N, I, O, H, W, ks, up, mma, ximg != nullptr, yimg != nullptr, rgb != nullptr, act, alpha}, p3d_conv_switches());
+    if (pl.end > workspace_bytes) return P3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    float* dco = (float*)workspace;
-    float* tmp = dco + (((size_t)N * O + 63) / 64) * 64;
-    // up = 2: the intermediate T has 2W + 1 columns, stored at a pitch of 2W + 4 floats with column ox at index ox + 1, so that the
-    // FIR pass reads 16-byte aligned windows (k_fir4x4_*); OW below is that PITCH for everything that indexes T
-    const int OH = (up == 2) ? 2 * H + 1 : H, OW = (up == 2) ? 2 * W + 4 : W;
-    const size_t out_elems = (size_t)N * O * OH * OW;
-    float* part = (up == 2) ? tmp + ((out_elems + 63) / 64) * 64 : tmp;
+    char* ws = (char*)workspace;
+    float* dco = (float*)(ws + pl.dcoef);
+    float* tmp = (float*)(ws + pl.inter);
+    float* part = (float*)(ws + pl.part);
     if (demodulate && dcoef_in) dco = const_cast<float*>(dcoef_in);  // precomputed by p3d_demod_coefs_f32 (one launch per network)
     else if (demodulate) {
         int waves = N * O;
         hipLaunchKernelGGL(k_demod, dim3((waves * 64 + 255) / 256), dim3(256), 0, st, w, styles, N, O, I, ks * ks, dco);
     }
-    const bool wide = wh && wsplit && ks == 3 && up == 1 && W >= p3d_w3_min_w();  // k_modconv_w3 / k_modconv_up3
-    const bool up3 = wh && wsplit && ks == 3 && up == 2 && up3_applies(I, O, W);  // k_modconv_up3 / k_modconv_up4
-    // k_modconv_up4 (round 6): transposed convolution + FIR pass + epilogue in one launch, no intermediate and no split-K — every
-    // up-sampling layer whose 8-row tiling alone gives the chip enough workgroups (the 64^2 .. 512^2 maps of the backbone and of
-    // the super-resolution); smaller maps keep the split-K form (k_modconv_up3 + reduction + FIR pass)
-    const bool up4 = up3 && (act == 0 || (alpha >= 0.0f && alpha <= 1.0f)) && up4_applies(N, I, O, H, W);
-    const int ksplit = up4 ? 1 : up3 ? choose_ksplit_up3(N, I, O, H, W)
-                           : choose_ksplit(N, I, O, up == 2 ? H + 1 : H, up == 2 ? W + 1 : W, wide ? WX_TW : CONV_TW);
-    // An fp32 input of a layer the pipelined kernel can run (O % 64 == 0) is first turned into the image that kernel stages from
-    // (one pass, 8 bytes per value; the generator's blocks hand over images and never come here): ONE kernel does the arithmetic
-    // of a layer whichever way its input arrives, so both ways give the same bits.
-    if ((up3 && !ximg) || (wide && !ximg && O % 64 == 0 && I % 16 == 0 && !p3d_env_no_w3())) {
-        char* img = (char*)(part + (ksplit > 1 ? ((size_t)ksplit * out_elems + 63) / 64 * 64 : 0));
-        img = (char*)(((uintptr_t)img + 255) & ~(uintptr_t)255);
+    if (pl.pre_image) {
         const long long tot = (long long)N * (I / 8) * H * W;
-        hipLaunchKernelGGL(k_act_to_image, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, styles, N, I, H * W, img, (long long)N * I * H * W * 2, sat);
-        ximg = img;
+        hipLaunchKernelGGL(k_act_to_image, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, styles, N, I, H * W, ws + pl.img, (long long)N * I * H * W * 2, sat);
+        ximg = ws + pl.img;
     }
+    const bool up4 = pl.main == ConvKernel::UP4_16 || pl.main == ConvKernel::UP4_8;
     ConvParams p;
     p.x = x; p.w = w; p.wh = wh; p.wsplit = wsplit; p.styles = styles; p.dcoef = demodulate ? dco : nullptr; p.noise = noise; p.bias = bias;
     p.N = N; p.I = I; p.O = O; p.H = H; p.W = W; p.ks = ks; p.noise_per_sample = noise_per_sample;
-    p.act = act; p.alpha = alpha; p.gain = gain; p.clamp = clamp; p.ksplit = ksplit; p.OH = OH; p.OW = OW; p.sat = sat;
+    p.act = act; p.alpha = alpha; p.gain = gain; p.clamp = clamp; p.ksplit = pl.ksplit; p.OH = pl.OH; p.OW = pl.OW; p.sat = sat;
     p.ximg = ximg; p.ximg_lo = (long long)N * I * H * W * 2; p.tox = up == 2 ? 1 : 0; p.wlayout = wlayout;
     p.rgbw = rgb ? rgb->w : nullptr; p.rgbs = rgb ? rgb->styles : nullptr; p.rgbp = rgb ? rgb->partial : nullptr; p.rgbo = rgb ? rgb->channels : 0;
-    static const bool xcd_order = !getenv("P3D_NO_XCD_ORDER");  // (A/B runs)
-    p.xcd = xcd_order ? 1 : 0;
-    // up = 1 with an image output: k_modconv_w3 writes it from its epilogue when it runs unsplit; otherwise a pass over y below
-    const bool w3_img = up == 1 && yimg && wide && ximg && O % 64 == 0 && ksplit == 1 && !p3d_env_no_w3();
-    // up = 2 into an image, unsplit, few input channels: the FIR pass and the epilogue run inside k_modconv_up3<true> (no
-    // intermediate).  Measured (tools/conv_layers_time.py, us): 32 -> 256 @128^2 -> 256^2 71 -> 56; 256 -> 128 @256^2 -> 512^2 240 -> 254:
-    // with a long K loop the filter's VALU work (76 us chip-wide) and the 1.42 x MFMA work of the overlapping tiles cost more than
-    // the intermediate's round trip.  P3D_UP3_FUSED=0/1 in the environment overrides the choice (tests, A/B runs).
-    const char* fused_env = getenv("P3D_UP3_FUSED");
-    const bool up3_fused = up3 && yimg && ksplit == 1 && (fused_env ? atoi(fused_env) != 0 : I <= 64);
-    p.yimg = (w3_img || up3_fused) ? yimg : nullptr; p.yimg_lo = (long long)N * O * H * W * 2; p.ystyles = ystyles; p.fir = fir;
-    // conv output goes to: y (up 1, no split), tmp (up 2, no split) or the partial buffer (split-K), raw unless final
-    float* conv_dst = (ksplit > 1) ? part : (up == 2 ? tmp : y);
-    p.y = conv_dst;
-    p.epilogue = (up == 1 && ksplit == 1) ? 1 : 0;
-    if (up == 1) {
-        p.GH = H; p.GW = W;
-        p3d_launch_conv_plain(p, st);
-    } else {  // stride-2 transposed conv into [N][O][2H+1][2W+1]: all four output phases in one launch
-        p.GH = H + 1; p.GW = W + 1;
-        if (up4) {
-            p.y = y; p.yimg = yimg;
-            return p3d_up4_launch(p, p3d_up4_shape(N, O, H, W), st);
-        }
-        if (up3_fused) {
-            p3d_launch_conv_up(p, 2, st);
-            return chk();
-        }
-        p3d_launch_conv_up(p, up3 ? 1 : 0, st);
-    }
-    // Split-K partial sums.  Up-sampling layer with a SHALLOW split (<= 8 slices: the 64^2 .. 256^2 layers at batch 1): the FIR pass
-    // below sums the slices while it loads its tiles — one launch and one round trip of the (2H+1)x(2W+1) intermediate less, the
-    // same slice-ordered sum.  Deep splits (the 4^2 .. 32^2 layers, up to 64 slices) keep the separate, chip-wide reduction:
-    // measured (profiles/history/r03_notes.txt) both a per-element slice loop inside the FIR pass (4.8 + 5.8 -> 37 us at 64 slices) and an
-    // in-launch last-arriver reduction of the plain convolutions (release / ticket / acquire: +15 .. +50 us per layer) lose to it.
-    // ... unless the FIR launch itself is a handful of workgroups (one per 32 x 32 tile and eight channels: 64 for 512 channels at 32^2,
-    // each then pulling eight slices of its tile through one CU: 17.9 us) — there the chip-wide reduction + a plain FIR pass are faster
-    static const long long fir_sums_min_wgs = getenv("P3D_FIR_SUMS_MIN_WGS") ? atoll(getenv("P3D_FIR_SUMS_MIN_WGS")) : 0;  // (measured with 128: 6.5 + 10.2 us instead of 18.2 at 32^2 — one more launch for 1.5 us: left off)
-    const long long fir_wgs = (long long)((2 * W + 31) / 32) * ((2 * H + 31) / 32) * ((long long)N * O / (yimg ? 8 : 1));
-    const bool fir_sums = up == 2 && ksplit > 1 && ksplit <= 8 && fir_wgs >= fir_sums_min_wgs;
-    if (ksplit > 1 && !fir_sums) {
+    p.xcd = 1;
+    p.yimg = pl.main_img ? yimg : nullptr; p.yimg_lo = (long long)N * O * H * W * 2; p.ystyles = ystyles; p.fir = fir;
+    // conv output goes to: y (up 1, no split; k_modconv_up4), the intermediate (up 2, no split) or the partials (split-K), raw unless final
+    p.y = up4 ? y : pl.ksplit > 1 ? part : up == 2 ? tmp : y;
+    p.epilogue = (up == 1 && pl.ksplit == 1) ? 1 : 0;
+    p.GH = up == 2 ? H + 1 : H; p.GW = up == 2 ? W + 1 : W;  // up = 2: all four output phases of the transposed conv in one launch
+    if (up == 1) p3d_launch_conv_plain(p, pl.main, pl.grid, st);
+    else if (up4) p3d_launch_conv_up4(p, pl.main, pl.grid, st);
+    else p3d_launch_conv_up(p, pl.main, pl.grid, st);
+    if (pl.reduce != ConvReduce::NONE) {
         ReduceParams r;
         r.part = part; r.y = (up == 2) ? tmp : y; r.dcoef = p.dcoef; r.noise = noise; r.bias = bias;
-        r.per_slice = (long long)out_elems; r.ksplit = ksplit; r.O = O; r.OHW = OH * OW; r.noise_per_sample = noise_per_sample;
+        r.per_slice = (long long)pl.out_elems; r.ksplit = pl.ksplit; r.O = O; r.OHW = pl.OH * pl.OW; r.noise_per_sample = noise_per_sample;
         r.act = act; r.epilogue = (up == 1) ? 1 : 0; r.alpha = alpha; r.gain = gain; r.clamp = clamp;
-        if (up == 1 && yimg && !w3_img && !getenv("P3D_NO_REDUCE_IMG")) {  // the sums, the epilogue and the next layer's image in one launch
-            hipLaunchKernelGGL(k_splitk_reduce_img, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, st, r, N, ystyles, (_Float16*)yimg,
-                               (long long)N * O * H * W, sat);
-            return chk();
-        }
-        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, st, r);
+        const dim3 g(pl.reduce_grid.x);
+        if (pl.reduce == ConvReduce::REDUCE_IMG)
+            hipLaunchKernelGGL(k_splitk_reduce_img, g, dim3(256), 0, st, r, N, ystyles, (_Float16*)yimg, (long long)N * O * H * W, sat);
+        else hipLaunchKernelGGL(k_splitk_reduce, g, dim3(256), 0, st, r);
     }
-    if (up == 1) {
-        if (yimg && !w3_img) {  // (split-K layers, channel counts the pipelined kernel does not take: the image from the finished y)
-            const long long tot = (long long)N * (O / 8) * H * W;
-            hipLaunchKernelGGL(k_act_to_image, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, y, ystyles, N, O, H * W, (char*)yimg,
-                               (long long)N * O * H * W * 2, sat);
-        }
-        return chk();
+    if (pl.tail == ConvTail::ACT_TO_IMAGE)
+        hipLaunchKernelGGL(k_act_to_image, dim3(pl.tail_grid.x), dim3(256), 0, st, y, ystyles, N, O, H * W, (char*)yimg, (long long)N * O * H * W * 2, sat);
+    else if (pl.tail != ConvTail::NONE) {
+        // FIR (pad 1; the caller passes the 4x4 filter already flipped and multiplied by up^2, upfirdn2d.py:193-196) + epilogue
+        FirParams q;
+        q.x = pl.fir_sums ? part : tmp; q.ksplit = pl.fir_sums ? pl.ksplit : 1; q.slice = (long long)pl.out_elems;
+        q.f = fir; q.y = y; q.dcoef = demodulate ? dco : nullptr; q.noise = noise; q.bias = bias;
+        q.NC = (long long)N * O; q.C = O; q.H = 2 * H + 1; q.W = 2 * W + 1; q.OH = 2 * H; q.OW = 2 * W; q.fh = 4; q.fw = 4; q.pitch = pl.OW; q.xoff = 1;
+        q.up = 1; q.down = 1; q.padx0 = 1; q.pady0 = 1; q.noise_per_sample = noise_per_sample; q.act = act; q.epilogue = 1;
+        q.alpha = alpha; q.gain = gain; q.clamp = clamp; q.nstyles = ystyles;
+        p3d_launch_fir_pass(q, pl.tail, pl.tail_grid, (char*)yimg, (long long)N * O * q.OH * q.OW * 2, sat, st);
     }
-    // FIR (pad 1; the caller passes the 4x4 filter already flipped and multiplied by up^2, upfirdn2d.py:193-196) + epilogue
-    FirParams q;
-    q.x = fir_sums ? part : tmp; q.ksplit = fir_sums ? ksplit : 1; q.slice = (long long)out_elems;
-    q.f = fir; q.y = y; q.dcoef = demodulate ? dco : nullptr; q.noise = noise; q.bias = bias;
-    q.NC = (long long)N * O; q.C = O; q.H = 2 * H + 1; q.W = 2 * W + 1; q.OH = 2 * H; q.OW = 2 * W; q.fh = 4; q.fw = 4; q.pitch = OW; q.xoff = 1;
-    q.up = 1; q.down = 1; q.padx0 = 1; q.pady0 = 1; q.noise_per_sample = noise_per_sample; q.act = act; q.epilogue = 1;
-    q.alpha = alpha; q.gain = gain; q.clamp = clamp; q.nstyles = ystyles;
-    p3d_launch_fir_pass(q, (char*)yimg, (long long)N * O * q.OH * q.OW * 2, sat, st);
     return chk();
+}
+
+extern "C" {
+
+int p3d_modconv2d_ex_f32(const p3d_conv_args* a, void* stream) {
+    if (!a) return P3D_E_ARG;
+    const void* wh = nullptr;
+    int wsplit = 0;
+    if (a->mma != P3D_CONV_MMA_F32) {
+        if (!a->w_f16) return P3D_E_ARG;
+        wsplit = a->mma == P3D_CONV_MMA_F16X2;
+        if (a->mma != P3D_CONV_MMA_F16 && !wsplit) return P3D_E_RANGE;
+        // a K chunk is 16 channels; 16-byte weight pieces (and the lo half of a two-term copy starts on one)
+        if (a->I % 16 != 0 || ((uintptr_t)a->w_f16 & 15) || (wsplit && ((size_t)a->O * a->I * a->ks * a->ks * 2) % 16 != 0)) return P3D_E_RANGE;
+        wh = a->w_f16;
+    }
+    if (a->x_img && !wsplit) return P3D_E_RANGE;
+    const RgbFuse rgb = {a->rgb_w, a->rgb_styles, a->rgb_partial, a->rgb_channels};
+    return modconv_impl(a->x, a->N, a->I, a->H, a->W, a->w, wh, wsplit, a->O, a->ks, a->styles, a->demodulate, a->demod_coefs, a->noise,
+                        a->noise_per_sample, a->bias, a->up, a->act, a->alpha, a->gain, a->clamp, a->fir, a->y, a->workspace, a->workspace_bytes,
+                        stream, (wsplit || a->y_img) ? (unsigned int*)a->saturated : nullptr, a->x_img, a->y_img, a->y_img_styles, &rgb, a->w_f16_layout);
+}
+
+// the positional entry points: one p3d_conv_args each, through the validation of p3d_modconv2d_ex_f32
+static int modconv_positional(int mma, const float* x, int N, int I, int H, int W, const float* w, const void* w_f16, int O, int ks,
+                              const float* styles, int demodulate, const float* demod_coefs, const float* noise, int noise_per_sample,
+                              const float* bias, int up, int act, float alpha, float gain, float clamp, const float* fir, float* y,
+                              void* workspace, size_t workspace_bytes, uint32_t* saturated, void* stream) {
+    p3d_conv_args a = {};
+    a.x = x; a.w = w; a.w_f16 = w_f16; a.styles = styles; a.demod_coefs = demod_coefs; a.noise = noise; a.bias = bias; a.fir = fir; a.y = y;
+    a.workspace = workspace; a.saturated = saturated; a.workspace_bytes = workspace_bytes;
+    a.N = N; a.I = I; a.H = H; a.W = W; a.O = O; a.ks = ks; a.up = up; a.demodulate = demodulate; a.noise_per_sample = noise_per_sample;
+    a.act = act; a.mma = mma; a.alpha = alpha; a.gain = gain; a.clamp = clamp;
+    return p3d_modconv2d_ex_f32(&a, stream);
 }
 
 int p3d_modconv2d_f32(const float* x, int N, int I, int H, int W, const float* w, int O, int ks, const float* styles,
                       int demodulate, const float* demod_coefs, const float* noise, int noise_per_sample, const float* bias, int up,
                       int act, float alpha, float gain, float clamp, const float* fir, float* y, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    return modconv_impl(x, N, I, H, W, w, nullptr, 0, O, ks, styles, demodulate, demod_coefs, noise, noise_per_sample, bias, up, act,
-                        alpha, gain, clamp, fir, y, workspace, workspace_bytes, stream);
+    return modconv_positional(P3D_CONV_MMA_F32, x, N, I, H, W, w, nullptr, O, ks, styles, demodulate, demod_coefs, noise, noise_per_sample,
+                              bias, up, act, alpha, gain, clamp, fir, y, workspace, workspace_bytes, nullptr, stream);
 }
 
 int p3d_demod_coefs_f32(const float* w2, const float* styles, const int32_t* table, int L, int N, int total_waves, float* d,
@@ -513,28 +398,8 @@ int p3d_modconv2d_f16mma_f32(const float* x, int N, int I, int H, int W, const f
                              const float* styles, int demodulate, const float* demod_coefs, const float* noise, int noise_per_sample, const float* bias,
                              int up, int act, float alpha, float gain, float clamp, const float* fir, float* y, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    if (!w_f16) return P3D_E_ARG;
-    if (I % 16 != 0 || ((uintptr_t)w_f16 & 15)) return P3D_E_RANGE;  // a K chunk is 16 channels; 16-byte weight pieces
-    return modconv_impl(x, N, I, H, W, w, w_f16, 0, O, ks, styles, demodulate, demod_coefs, noise, noise_per_sample, bias, up, act, alpha,
-                        gain, clamp, fir, y, workspace, workspace_bytes, stream);
-}
-
-int p3d_modconv2d_ex_f32(const p3d_conv_args* a, void* stream) {
-    if (!a) return P3D_E_ARG;
-    const void* wh = nullptr;
-    int wsplit = 0;
-    if (a->mma != P3D_CONV_MMA_F32) {
-        if (!a->w_f16) return P3D_E_ARG;
-        wsplit = a->mma == P3D_CONV_MMA_F16X2;
-        if (a->mma != P3D_CONV_MMA_F16 && !wsplit) return P3D_E_RANGE;
-        if (a->I % 16 != 0 || ((uintptr_t)a->w_f16 & 15) || (wsplit && ((size_t)a->O * a->I * a->ks * a->ks * 2) % 16 != 0)) return P3D_E_RANGE;
-        wh = a->w_f16;
-    }
-    if (a->x_img && !wsplit) return P3D_E_RANGE;
-    const RgbFuse rgb = {a->rgb_w, a->rgb_styles, a->rgb_partial, a->rgb_channels};
-    return modconv_impl(a->x, a->N, a->I, a->H, a->W, a->w, wh, wsplit, a->O, a->ks, a->styles, a->demodulate, a->demod_coefs, a->noise,
-                        a->noise_per_sample, a->bias, a->up, a->act, a->alpha, a->gain, a->clamp, a->fir, a->y, a->workspace, a->workspace_bytes,
-                        stream, (wsplit || a->y_img) ? (unsigned int*)a->saturated : nullptr, a->x_img, a->y_img, a->y_img_styles, &rgb, a->w_f16_layout);
+    return modconv_positional(P3D_CONV_MMA_F16, x, N, I, H, W, w, w_f16, O, ks, styles, demodulate, demod_coefs, noise, noise_per_sample,
+                              bias, up, act, alpha, gain, clamp, fir, y, workspace, workspace_bytes, nullptr, stream);
 }
 
 size_t p3d_act_image_bytes(int N, int C, int H, int W) { return (size_t)N * C * H * W * 4; }
@@ -562,10 +427,8 @@ int p3d_modconv2d_f16x2mma_f32(const float* x, int N, int I, int H, int W, const
                                const float* styles, int demodulate, const float* demod_coefs, const float* noise, int noise_per_sample,
                                const float* bias, int up, int act, float alpha, float gain, float clamp, const float* fir, float* y,
                                void* workspace, size_t workspace_bytes, uint32_t* saturated, void* stream) {
-    if (!w_f16x2) return P3D_E_ARG;
-    if (I % 16 != 0 || ((uintptr_t)w_f16x2 & 15) || ((size_t)O * I * ks * ks * 2) % 16 != 0) return P3D_E_RANGE;
-    return modconv_impl(x, N, I, H, W, w, w_f16x2, 1, O, ks, styles, demodulate, demod_coefs, noise, noise_per_sample, bias, up, act,
-                        alpha, gain, clamp, fir, y, workspace, workspace_bytes, stream, (unsigned int*)saturated);
+    return modconv_positional(P3D_CONV_MMA_F16X2, x, N, I, H, W, w, w_f16x2, O, ks, styles, demodulate, demod_coefs, noise, noise_per_sample,
+                              bias, up, act, alpha, gain, clamp, fir, y, workspace, workspace_bytes, saturated, stream);
 }
 
 }  // extern "C"

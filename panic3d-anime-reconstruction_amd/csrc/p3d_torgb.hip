@@ -291,8 +291,8 @@ int p3d_torgb_f32(const float* x, int N, int I, int H, int W, const float* w_t, 
     // waves split K) below that
     const bool ks = (long long)N * ((HW + 127) / 128) < 512;
     // small maps of a 96-channel layer: one workgroup per 32-channel tile while that still leaves the chip underfilled
-    const bool ms = ks && MT == 3 && (long long)N * ((HW + 31) / 32) * 3 <= 1024 && !getenv("P3D_NO_TORGB_MS");
-    const bool pre = ms && I <= 8 * TG_KC && !getenv("P3D_NO_TORGB_PRE");  // everything requested up front (k_torgb<..., PRE>)
+    const bool ms = ks && MT == 3 && (long long)N * ((HW + 31) / 32) * 3 <= 1024;
+    const bool pre = ms && I <= 8 * TG_KC;  // everything requested up front (k_torgb<..., PRE>)
     const size_t lds = (size_t)(2 * TG_KC * 32 * (ms ? 1 : MT) + (pre ? 8 * TG_KC : ((I + 63) / 64) * 64)) * 4;
     dim3 grid((unsigned)(ks ? (HW + 31) / 32 : (HW + 127) / 128), (unsigned)N, ms ? 3u : 1u);
     if (lds > 64 * 1024) return P3D_E_RANGE;  // (53 KB at I = 1024, O = 96: inside the default dynamic-LDS limit, no per-device attribute to set)

@@ -949,7 +949,7 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, padding=0, resample_fi
     ximg = x if isinstance(x, ActImage) else None
     if ximg is not None:
         if up == 2 and not takes_image_up(ximg.shape[1], weight.shape[0], ximg.shape[3]):
-            raise RuntimeError("modulated_conv2d: the library does not stage this up-sampling layer from an ActImage (p3d_conv_takes_image: I % 16 == 0, O % 32 == 0, W >= P3D_UP3_MIN_W)")
+            raise RuntimeError("modulated_conv2d: the library does not stage this up-sampling layer from an ActImage (p3d_conv_takes_image: I % 16 == 0, O % 32 == 0, W >= 4)")
         if weight_f16 is None or weight_f16.ndim != 4 or (demodulate and dcoef is None):
             raise RuntimeError("modulated_conv2d: an ActImage input needs two-term weights (conv_weights_to_f16(split=True)) and precomputed dcoef")
         x = None

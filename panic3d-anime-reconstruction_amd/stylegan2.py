@@ -117,14 +117,13 @@ DEFAULT_CONV_MMA = os.environ.get("P3D_CONV_MMA", "x2")
 DEFAULT_CONV_MMA_1X1 = os.environ.get("P3D_CONV_MMA_1X1", "f32")  # the 1x1 ToRGB layers (A/B knob, measured in round 3)
 
 
-# The activation IMAGE (ops.ActImage; csrc/p3d_synthesis.hip "activation IMAGE"): in a block whose map is >= IMG_MIN_RES^2, conv0's
+# The activation IMAGE (ops.ActImage; csrc/p3d_synthesis.hip "activation IMAGE"): in a block whose conv1 takes one (ops.takes_image), conv0's
 # last pass writes conv1's two-term operand directly (conv1's styles applied, hi / lo split done) instead of an fp32 tensor that
 # conv1 would modulate and split again in each of its channel-tile workgroups.  Bit-identical results; P3D_CONV_IMG=0 for A/B runs.
 CONV_IMG = os.environ.get("P3D_CONV_IMG", "1") != "0"
 # StylePlan returns the previous call's result for the same ws object (views of one subject).  Off: every pass computes its styles
 # (the pass timings of tools/bench_backbone.py, graph_backbone.py, profile_backbone.py are taken that way).
 STYLE_MEMO = os.environ.get("P3D_STYLE_MEMO", "1") != "0"
-IMG_MIN_RES = int(os.environ.get("P3D_W3_MIN_W", "32"))  # (the library's own rule is asked as well: ops.takes_image)
 # A block of <= 4 image channels (the super-resolution's) computes its ToRGB sums in conv1's epilogue (ops.conv_fuses_torgb): the
 # activation is not read back — and not written when nobody else reads it.  fp32-class agreement with the stand-alone ToRGB launch
 # (another summation order); P3D_TORGB_RIDES=0 for A/B runs.
@@ -146,19 +145,19 @@ def set_noise_pool(state):
 
 
 def switch_state():
-    """The process-wide switches above that decide WHICH launches a pass issues, as one tuple (seven global reads, no module walk):
+    """The process-wide switches above that decide WHICH launches a pass issues, as one tuple (six global reads, no module walk):
     part of the key of a captured view (TriPlaneGenerator._replay_view), so a capture never outlives a switch it was made under."""
-    return (DEFAULT_CONV_MMA, DEFAULT_CONV_MMA_1X1, CONV_IMG, IMG_MIN_RES, TORGB_RIDES, NOISE_POOL, STYLE_MEMO)
+    return (DEFAULT_CONV_MMA, DEFAULT_CONV_MMA_1X1, CONV_IMG, TORGB_RIDES, NOISE_POOL, STYLE_MEMO)
 
 
 def _takes_image(layer, res):
-    """A plain 3x3 layer that can stage its input from an activation image: two-term operands, 16-channel K chunks, a map of at
-    least IMG_MIN_RES columns (the wide-tile kernel)."""
+    """A plain 3x3 layer that can stage its input from an activation image: two-term operands and the library's rule
+    (ops.takes_image: 16-channel K chunks, a map wide enough for the wide-tile kernel)."""
     mode = layer.__dict__.get("mma_f16")
     if mode is None:
         mode = "x2" if DEFAULT_CONV_MMA == "x2" else False
     w = layer._parameters["weight"]
-    return CONV_IMG and mode == "x2" and layer.up == 1 and w.shape[-1] == 3 and res >= IMG_MIN_RES and ops.takes_image(layer.in_channels, w.shape[0], res, 1)
+    return CONV_IMG and mode == "x2" and layer.up == 1 and w.shape[-1] == 3 and ops.takes_image(layer.in_channels, w.shape[0], res, 1)
 
 
 def _next_conv0_styles(next_block, next_pre, res):

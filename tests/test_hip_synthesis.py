@@ -744,8 +744,6 @@ def test_up4_one_launch_up_layer_equals_the_two_pass_form(hip, monkeypatch, N, I
               clamp=1.5 if N > 1 else None)
     ximg = ops.act_to_image(x, s0)
     monkeypatch.setenv("P3D_UP4_RPW", rpw)
-    monkeypatch.setenv("P3D_UP4_MIN_WGS", "0")
-    monkeypatch.setenv("P3D_UP4_MIN_I", "0")
     monkeypatch.setenv("P3D_UP3_FUSED", "0")
     out = {}
     for mode in ("0", "1"):

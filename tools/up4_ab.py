@@ -30,8 +30,6 @@ def main():
     f = ops.setup_filter((1, 3, 3, 1)).to(dev)
     shapes = [("sr.block1.conv0", 256, 128, 256), ("sr.block0.conv0", 32, 256, 128), ("b256.conv0", 256, 128, 128), ("b128.conv0", 512, 256, 64),
               ("b64.conv0", 512, 512, 32), ("b32.conv0", 512, 512, 16)]
-    os.environ["P3D_UP4_MIN_WGS"] = "0"
-    os.environ["P3D_UP4_MIN_I"] = "0"
     for name, I, O, H in shapes:
         x = torch.randn(1, I, H, H, device=dev)
         w = torch.randn(O, I, 3, 3, device=dev)
