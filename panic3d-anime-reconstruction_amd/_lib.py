@@ -113,6 +113,15 @@ GRAD_SIGNATURES = {
     "p3d_triplane_decode_backward_f32": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _P, _P, C.POINTER(Opts), _P, _P, _P, _P, _P, _P, _P,
                                               _P, _Z, _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_synthesis_grad.h declares (the synthesis layers' backward).  A third table:
+# the two above mirror their headers exactly.
+SYN_GRAD_SIGNATURES = {
+    "p3d_bias_act_backward_f32": (_I, [_P, _P, _I, _I, _L, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "p3d_conv_dgrad_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "p3d_mod_backward_f32": (_I, [_P, _P, _I, _I, _L, _P, _P, _P]),
+    "p3d_conv_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "p3d_conv_wgrad_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+}
 P3D_GRAD_STATS_BYTES = 256  # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
 
 _LIB = None
@@ -132,7 +141,7 @@ def lib():
                 print(f"panic3d_amd: {SO} does not match csrc/ (source hash): rebuilding", file=sys.stderr)
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

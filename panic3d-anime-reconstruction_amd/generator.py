@@ -4,9 +4,11 @@ checkpoint's init kwargs and copy the parameters by name), with the backbone on 
 (stylegan2.py), the volumetric renderer on the fused HIP kernel (renderer.py) and the super-resolution blocks on the same
 modulated-conv kernel.
 
-The backbone and the super-resolution are inference-only (`image` carries no gradient).  With grad enabled, `image_raw`,
-`image_depth`, `image_weights` and `image_xyz` carry gradients through the renderer's HIP backward to the decoder parameters
-(and to the planes when a caller renders planes that require grad; renderer.py).  Not mirrored: `sample` (broken in the reference, triplane.py:254-271).  The `paste_front`
+The super-resolution is inference-only (`image` carries no gradient).  With grad enabled, `image_raw`, `image_depth`,
+`image_weights` and `image_xyz` carry gradients through the renderer's HIP backward to the decoder parameters and the planes
+(renderer.py), and from the planes through the synthesis network's HIP backward (stylegan2.SynthesisNetwork) to
+`ws`, the backbone's synthesis parameters, latent injections and conditioning tensors that require grad.  The mapping network
+stays inference-only (`ws` is the leaf), and so does the staged density-noise path.  Not mirrored: `sample` (broken in the reference, triplane.py:254-271).  The `paste_front`
 post-process (triplane.py:555-691) lives in paste.py.
 """
 import os
@@ -66,6 +68,11 @@ class SuperresolutionHybrid8XDC(torch.nn.Module):
                                                img_channels=3, is_last=True, conv_clamp=clamp, **block_kwargs)
 
     def forward(self, rgb, x, ws, **block_kwargs):
+        """Inference-only: runs without autograd whatever the caller's grad mode (the returned image carries no gradient)."""
+        with torch.no_grad():
+            return self._forward(rgb, x, ws, **block_kwargs)
+
+    def _forward(self, rgb, x, ws, **block_kwargs):
         ws_in = ws
         ws = ws[:, -1:, :].expand(-1, 3, -1)  # (`.repeat(1, 3, 1)` of superresolution.py:283 without the copy: the layers only read it)
         if x.shape[-1] != self.input_resolution:
@@ -218,7 +225,7 @@ class TriPlaneGenerator(torch.nn.Module):
         else:
             planes = self._planes(ws, cond, latent_injection, stop_level, **synthesis_kwargs)
         if cache_backbone:
-            self._last_planes = planes
+            self._last_planes = planes.detach()  # (values only: a later call must not reach back into this call's graph)
         many_views = len(planes) == 1 and N > 1
         if many_views:
             # extension: V views of ONE subject in one call (ws / cond of batch 1, V cameras).  The planes are synthesised once
@@ -451,7 +458,7 @@ class TriPlaneGenerator(torch.nn.Module):
             self._domain_begin(ws.device)
             planes = self._planes(ws, cond, **synthesis_kwargs)
             self._domain_end(cond)
-            self._last_planes = planes if reuse else self._last_planes
+            self._last_planes = planes.detach() if reuse else self._last_planes  # (values only, as in _synthesis_impl)
         return self.renderer.run_model(planes, self.decoder, coordinates, directions, self.rendering_kwargs)
 
     def forward(self, z, c, cond, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None,

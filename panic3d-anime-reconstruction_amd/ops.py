@@ -672,7 +672,14 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
 
 
 def upsample2d(x, f, up=2, padding=0, flip_filter=False, gain=1):
-    """upfirdn2d.upsample2d (upfirdn2d.py:315-350)."""
+    """upfirdn2d.upsample2d (upfirdn2d.py:315-350).  Differentiable in x under autograd (the adjoint is upfirdn2d with the flipped
+    filter, upfirdn2d.py:236-245)."""
+    if _wants_grad(x):
+        return _Upsample2dFn.apply(x, (f, up, padding, flip_filter, gain))
+    return _upsample2d_impl(x, f, up, padding, flip_filter, gain)
+
+
+def _upsample2d_impl(x, f, up=2, padding=0, flip_filter=False, gain=1):
     px0, px1, py0, py1 = _parse_padding(padding)
     fh, fw = f.shape
     p = [px0 + (fw + up - 1) // 2, px1 + (fw - up) // 2, py0 + (fh + up - 1) // 2, py1 + (fh - up) // 2]
@@ -700,7 +707,14 @@ def upsample2d_add(x, f, add=None):
 
 
 def torgb_weights(weight):
-    """ToRGB weights [O,I,1,1] -> the transposed, channel-padded [I, 32 or 96] copy p3d_torgb_f32 streams (made once per layer)."""
+    """ToRGB weights [O,I,1,1] -> the transposed, channel-padded [I, 32 or 96] copy p3d_torgb_f32 streams (made once per layer).
+    Under autograd (weight requires grad) the copy carries the gradient back to weight."""
+    if _wants_grad(weight):
+        return _TorgbWeightsFn.apply(weight)
+    return _torgb_weights_impl(weight)
+
+
+def _torgb_weights_impl(weight):
     weight = _chk(weight, "weight")
     O, I = weight.shape[0], weight.shape[1]
     if weight.shape[2:] != (1, 1) or O > 96:
@@ -714,7 +728,13 @@ def torgb_weights(weight):
 def torgb(x, weight_t, out_channels, styles, bias=None, clamp=None, skip=None, skip_filter=None):
     """ToRGBLayer.forward (networks_stylegan2.py:366-380) + the skip connection of SynthesisBlock.forward (:476-478) in ONE launch:
     `upsample2d(skip, skip_filter) + (conv1x1(x * styles) + bias)`.  weight_t from torgb_weights; styles [N,I] already multiplied
-    by the layer's weight_gain; skip [N,O,H/2,W/2] or None."""
+    by the layer's weight_gain; skip [N,O,H/2,W/2] or None.  Differentiable under autograd (_TorgbFn: the HIP backward)."""
+    if _wants_grad(x, weight_t, styles, bias, skip):
+        return _TorgbFn.apply(x, weight_t, styles, bias, skip, (int(out_channels), clamp, skip_filter))
+    return _torgb_impl(x, weight_t, out_channels, styles, bias, clamp, skip, skip_filter)
+
+
+def _torgb_impl(x, weight_t, out_channels, styles, bias=None, clamp=None, skip=None, skip_filter=None):
     x, weight_t, styles = _chk(x, "x"), _chk(weight_t, "weight_t"), _chk(styles, "styles")
     N, I, H, W = x.shape
     O = int(out_channels)
@@ -946,6 +966,20 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, padding=0, resample_fi
     rgb_weight [R<=4,O] + rgb_styles [N,O] (plain 3x3 layer with an ActImage input, only where conv_fuses_torgb(...) says so): the
     block's ToRGB layer rides on this launch — the call returns (y, image or None, partial [O/64,N,R,H,W]) and torgb_combine(partial,
     ...) finishes the ToRGB layer; want_y=False: y is not written (None is returned in its place)."""
+    if _wants_grad(x if isinstance(x, torch.Tensor) else None, weight, styles, noise, bias, dcoef):
+        # under autograd: the HIP backward (_ModConvFn); the hand-overs below are inference-only
+        if isinstance(x, ActImage) or next_styles is not None or rgb_weight is not None:
+            raise RuntimeError("modulated_conv2d: activation images, next_styles and rgb_weight are inference-only (call under torch.no_grad())")
+        return _ModConvFn.apply(x, weight, styles, dcoef, bias, noise,
+                                dict(up=int(up), padding=padding, resample_filter=resample_filter, demodulate=bool(demodulate), act=act, gain=gain,
+                                     clamp=clamp, weight_f16=weight_f16, saturated=saturated))
+    return _modulated_conv2d_impl(x, weight, styles, noise, up, padding, resample_filter, demodulate, bias, act, gain, clamp, weight_f16,
+                                  dcoef, saturated, next_styles, rgb_weight, rgb_styles, want_y)
+
+
+def _modulated_conv2d_impl(x, weight, styles, noise=None, up=1, padding=0, resample_filter=None, demodulate=True,
+                           bias=None, act="linear", gain=None, clamp=None, weight_f16=None, dcoef=None, saturated=None,
+                           next_styles=None, rgb_weight=None, rgb_styles=None, want_y=True):
     ximg = x if isinstance(x, ActImage) else None
     if ximg is not None:
         if up == 2 and not takes_image_up(ximg.shape[1], weight.shape[0], ximg.shape[3]):
@@ -1032,3 +1066,207 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, padding=0, resample_fi
     if rgb:
         return y, yimg, rgbp
     return (y, yimg) if both else (yimg if out_image else y)
+
+
+# ======================================================================================================================
+# Backward of the synthesis layers (include/p3d_synthesis_grad.h).  The autograd Functions sit inside the
+# operators above: a call under autograd with an input that requires grad runs the same forward launches and records the
+# HIP backward; every other call is unchanged.
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def _sg_workspace(device, nbytes):
+    return torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=device)
+
+
+def bias_act_backward(y, g_y, act, alpha, gain, clamp, dscale=None, want_noise=False):
+    """p3d_bias_act_backward_f32: (g_z * dscale [N,C,...], sum over pixels of g_z [N,C], channel sum of g_z [N,pixels] or None)."""
+    y, g_y = _chk(y, "y"), _chk(g_y, "g_y")
+    N, Cc = y.shape[0], y.shape[1]
+    HW = y.numel() // (N * Cc)
+    out = torch.empty_like(y)
+    gb = torch.empty((N, Cc), dtype=torch.float32, device=y.device)
+    gn = torch.empty((N, HW), dtype=torch.float32, device=y.device) if want_noise else None
+    if dscale is not None:
+        dscale = _chk(dscale, "dscale")
+    with _on(y.device):
+        rc = _lib.lib().p3d_bias_act_backward_f32(_p(y), _p(g_y), N, Cc, HW, int(act), float(alpha), float(gain),
+                                                  float(clamp if clamp is not None else -1), _p(dscale), _p(out), _p(gb), _p(gn), _stream())
+    _lib.check(rc, "p3d_bias_act_backward_f32")
+    return out, gb, gn
+
+
+def conv_dgrad(g, wk, Co, Ho, Wo, stride, pad):
+    """p3d_conv_dgrad_f32: g [N,Ci,Hi,Wi], wk [taps,Ci,Co] -> [N,Co,Ho,Wo]."""
+    g, wk = _chk(g, "g"), _chk(wk, "wk")
+    N, Ci, Hi, Wi = g.shape
+    out = torch.empty((N, int(Co), int(Ho), int(Wo)), dtype=torch.float32, device=g.device)
+    with _on(g.device):
+        rc = _lib.lib().p3d_conv_dgrad_f32(_p(g), N, Ci, Hi, Wi, _p(wk), int(wk.shape[0]), int(Co), int(Ho), int(Wo), int(stride), int(pad),
+                                           _p(out), _stream())
+    _lib.check(rc, "p3d_conv_dgrad_f32")
+    return out
+
+
+def mod_backward(x, s, g):
+    """p3d_mod_backward_f32: returns g_s [N,C] = sum over pixels of x * g and multiplies g (contiguous, written in place) by s."""
+    x, s = _chk(x, "x"), _chk(s, "s")
+    if not g.is_contiguous():
+        raise RuntimeError("mod_backward: g is updated in place and must be contiguous")
+    N, Cc = x.shape[0], x.shape[1]
+    gs = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.lib().p3d_mod_backward_f32(_p(x), _p(s), N, Cc, x.numel() // (N * Cc), _p(g), _p(gs), _stream())
+    _lib.check(rc, "p3d_mod_backward_f32")
+    return gs
+
+
+def conv_wgrad(g, gmap, x, s, xmap, taps, domain, wk=None, dscale=None):
+    """p3d_conv_wgrad_f32: g [N,O,Hg,Wg] with its index map gmap = (stride, tap step, pad), x [N,I,Hx,Wx] * s [N,I] with xmap, over the
+    pixel domain (Hd, Wd) -> (dw [taps,O,I], g_d [N,O] when wk [taps,O,I] and dscale [N,O] are given, else None)."""
+    g, x = _chk(g, "g"), _chk(x, "x")
+    N, O, Hg, Wg = g.shape
+    I, Hx, Wx = x.shape[1], x.shape[2], x.shape[3]
+    Hd, Wd = domain
+    s = _chk(s, "s") if s is not None else None
+    L = _lib.lib()
+    wsb = L.p3d_conv_wgrad_workspace_bytes(N, O, I, int(taps), int(Hd), int(Wd))
+    if wsb == 0:
+        raise RuntimeError("conv_wgrad: sizes out of range")
+    ws = _sg_workspace(g.device, wsb)
+    dw = torch.empty((int(taps), O, I), dtype=torch.float32, device=g.device)
+    gd = None
+    if wk is not None:
+        wk, dscale = _chk(wk, "wk"), _chk(dscale, "dscale")
+        gd = torch.empty((N, O), dtype=torch.float32, device=g.device)
+    with _on(g.device):
+        rc = L.p3d_conv_wgrad_f32(_p(g), Hg, Wg, *(int(v) for v in gmap), _p(x), _p(s), Hx, Wx, *(int(v) for v in xmap), N, O, I, int(taps),
+                                  int(Hd), int(Wd), _p(dw), _p(wk), _p(dscale), _p(gd), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_conv_wgrad_f32")
+    return dw, gd
+
+
+def _upfirdn2d_adjoint(g, f, up, down, padding, flip_filter, gain, in_hw):
+    """The adjoint of upfirdn2d(x [.., in_hw], f, up, down, padding, flip_filter, gain) applied to g (upfirdn2d.py:236-245)."""
+    px0, px1, py0, py1 = _parse_padding(padding)
+    fh, fw = f.shape
+    ih, iw = in_hw
+    oh, ow = g.shape[-2:]
+    p = [fw - px0 - 1, iw * up - ow * down + px0 - up + 1, fh - py0 - 1, ih * up - oh * down + py0 - up + 1]
+    return upfirdn2d(g.contiguous(), f, up=down, down=up, padding=p, flip_filter=not flip_filter, gain=gain)
+
+
+class _Upsample2dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, meta):
+        f, up, padding, flip_filter, gain = meta
+        ctx.meta, ctx.hw = meta, tuple(x.shape[-2:])
+        return _upsample2d_impl(x, f, up, padding, flip_filter, gain)
+
+    @staticmethod
+    def backward(ctx, gy):
+        f, up, padding, flip_filter, gain = ctx.meta
+        px0, px1, py0, py1 = _parse_padding(padding)
+        fh, fw = f.shape
+        p = [px0 + (fw + up - 1) // 2, px1 + (fw - up) // 2, py0 + (fh + up - 1) // 2, py1 + (fh - up) // 2]
+        return _upfirdn2d_adjoint(gy, f, up, 1, p, flip_filter, gain * up * up, ctx.hw), None
+
+
+class _TorgbWeightsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight):
+        ctx.shape = tuple(weight.shape)
+        return _torgb_weights_impl(weight)
+
+    @staticmethod
+    def backward(ctx, gwt):
+        O, I = ctx.shape[0], ctx.shape[1]
+        return gwt[:, :O].t().reshape(ctx.shape).contiguous()
+
+
+class _TorgbFn(torch.autograd.Function):
+    """ToRGB (+ skip) backward: the clamp mask from the recomputed pre-clamp sums (the forward writes only the image), the skip
+    image's adjoint on upfirdn2d (down 2, flipped filter), data and weight gradients on the matrix cores."""
+
+    @staticmethod
+    def forward(ctx, x, weight_t, styles, bias, skip, meta):
+        O, clamp, skip_filter = meta
+        ctx.meta = meta
+        ctx.save_for_backward(x, weight_t, styles, bias)
+        ctx.skip_hw = None if skip is None else tuple(skip.shape[-2:])
+        return _torgb_impl(x, weight_t, O, styles, bias, clamp, skip, skip_filter)
+
+    @staticmethod
+    def backward(ctx, gimg):
+        x, weight_t, styles, bias = ctx.saved_tensors
+        O, clamp, skip_filter = ctx.meta
+        x, styles, g = x.contiguous(), styles.contiguous(), gimg.contiguous()
+        N, I, H, W = x.shape
+        g_skip = None
+        if ctx.skip_hw is not None and ctx.needs_input_grad[4]:
+            g_skip = _upfirdn2d_adjoint(g, skip_filter, 2, 1, [2, 1, 2, 1], False, 4.0, ctx.skip_hw)
+        ylin = _torgb_impl(x, weight_t, O, styles, bias, None, None, None) if clamp is not None else g
+        gz, gb, _ = bias_act_backward(ylin, g, 0, 0.0, 1.0, clamp)
+        w = weight_t[:, :O].t().contiguous().view(1, O, I)
+        gx = conv_dgrad(gz, w, I, H, W, 1, 0)
+        gs = mod_backward(x, styles, gx)
+        dw, _ = conv_wgrad(gz, (1, 0, 0), x, styles, (1, 0, 0), 1, (H, W))
+        gwt = torch.zeros_like(weight_t)
+        gwt[:, :O] = dw[0].t()
+        return gx, gwt, gs, (gb.sum(0) if bias is not None else None), g_skip, None
+
+
+class _ModConvFn(torch.autograd.Function):
+    """SynthesisLayer backward: bias_act from the output y (g_z * d), the FIR adjoint of an up-sampling layer,
+    the data gradient (plain: flipped weights, stride 1; up: stride-2 correlation), the modulation (g_s, g_x = g_xs * s), the
+    weight gradient split over pixels, and g_d[n,o] = sum W * dW_n / d."""
+
+    @staticmethod
+    def forward(ctx, x, weight, styles, dcoef, bias, noise, kw):
+        k = dict(kw)
+        y = _modulated_conv2d_impl(x, weight, styles, noise=noise, up=k["up"], padding=k["padding"], resample_filter=k["resample_filter"],
+                                   demodulate=k["demodulate"], bias=bias, act=k["act"], gain=k["gain"], clamp=k["clamp"],
+                                   weight_f16=k["weight_f16"], dcoef=dcoef, saturated=k["saturated"])
+        if k["demodulate"] and dcoef is None:
+            raise RuntimeError("modulated_conv2d under autograd: pass the demodulation coefficients (dcoef)")
+        ctx.kw = k
+        ctx.noise_shape = None if noise is None else tuple(noise.shape)
+        ctx.save_for_backward(x, weight, styles, dcoef, bias, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, styles, dcoef, bias, y = ctx.saved_tensors
+        k = ctx.kw
+        x, styles = x.contiguous(), styles.contiguous()
+        N, I, H, W = x.shape
+        O, ks = weight.shape[0], weight.shape[-1]
+        up, taps = k["up"], weight.shape[-1] * weight.shape[-2]
+        idx, da, dg = _ACTS[k["act"]]
+        gain = float(k["gain"] if k["gain"] is not None else dg)
+        d = dcoef.reshape(N, O).contiguous() if k["demodulate"] else None
+        want_noise = ctx.noise_shape is not None and ctx.needs_input_grad[5]
+        gz, gb, gn = bias_act_backward(y, gy.contiguous(), idx, da, gain, k["clamp"], dscale=d, want_noise=want_noise)
+        wk = weight.detach().permute(2, 3, 0, 1).reshape(taps, O, I).contiguous()  # [tap][o][i]
+        if up == 2:
+            G = _upfirdn2d_adjoint(gz, k["resample_filter"], 1, 1, 1, False, 4.0, (2 * H + 1, 2 * W + 1))  # [N,O,2H+1,2W+1]
+            gx = conv_dgrad(G, wk, I, H, W, 2, 0)
+            gmap, xmap = (2, 1, 0), (1, 0, 0)
+        elif ks == 3:
+            G = gz
+            gx = conv_dgrad(G, wk.flip(0).contiguous(), I, H, W, 1, 1)
+            gmap, xmap = (1, 0, 0), (1, 1, 1)
+        else:
+            G = gz
+            gx = conv_dgrad(G, wk, I, H, W, 1, 0)
+            gmap, xmap = (1, 0, 0), (1, 0, 0)
+        gs = mod_backward(x, styles, gx)
+        dw, gd = conv_wgrad(G, gmap, x, styles, xmap, taps, (H, W), wk=wk if d is not None else None, dscale=d)
+        gw = dw.view(ks, ks, O, I).permute(2, 3, 0, 1).contiguous()
+        g_noise = None
+        if want_noise:
+            ns = ctx.noise_shape
+            n_el = int(np.prod(ns))
+            g_noise = (gn if n_el == gn.numel() else gn.sum(0)).reshape(ns)
+        return (gx, gw, gs, (gd.view_as(dcoef) if gd is not None else None), (gb.sum(0) if bias is not None else None), g_noise, None)

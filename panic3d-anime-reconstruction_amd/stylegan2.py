@@ -3,8 +3,9 @@
 Mirrors the module tree and parameter names of training/networks_stylegan2.py (FullyConnectedLayer :102-133,
 MappingNetwork :199-296, SynthesisLayer :299-360, ToRGBLayer :363-383, SynthesisBlock :388-487, SynthesisNetwork
 :492-725, Generator :729-757) so that `misc.copy_params_and_buffers(..., require_all=True)` / `load_state_dict` of a
-PAniC-3D checkpoint works unchanged.  Inference only, fp32 only (the backbone runs with num_fp16_res=0:
-trainers/train_eclustrousC.py:253,553).  All convolution-shaped work runs in libpanic3d_hip.so: each SynthesisLayer /
+PAniC-3D checkpoint works unchanged.  fp32 only (the backbone runs with num_fp16_res=0: trainers/train_eclustrousC.py:253,553).
+The mapping network is inference-only; SynthesisNetwork.forward records a HIP backward when autograd records and ws, a parameter,
+a latent injection or a conditioning tensor requires grad.  All convolution-shaped work runs in libpanic3d_hip.so: each SynthesisLayer /
 ToRGBLayer is ONE fused call (modulation, conv on the matrix cores, demodulation, noise, bias, lrelu, gain, clamp);
 the tiny fully-connected layers (w -> styles, mapping) stay on torch matmul.
 """
@@ -248,6 +249,8 @@ class SynthesisLayer(_CacheFree):
     def _const_noise(self):
         """`noise_const * noise_strength` (networks_stylegan2.py:346), once per parameter version instead of once per call."""
         nc, ns = self._buffers["noise_const"], self._parameters["noise_strength"]  # (dict reads: nn.Module.__getattr__ is ~10x slower)
+        if torch.is_grad_enabled() and ns.requires_grad:  # under autograd: the same product, recorded (and not cached)
+            return (nc * ns).contiguous()
         key = (nc.data_ptr(), nc._version, ns.data_ptr(), ns._version)
         hit = self.__dict__.get("_noise_cache")
         if hit is None or hit[0] != key or not memo.enabled():
@@ -307,10 +310,15 @@ class NoisePool:
             hit = self._scale[(N, dev)] = (key, sc.contiguous(), offs, o)
         return hit
 
-    def draw(self, N, dev):
-        """Start a pass: draw and scale the noise of every layer for batch size N."""
+    def draw(self, N, dev, grad=False):
+        """Start a pass: draw and scale the noise of every layer for batch size N.  grad: the strengths are multiplied in as recorded
+        torch ops (the same products: the draw's values are the no-grad call's)."""
         _, sc, offs, total = self._scales(N, dev)
-        self._cur = (torch.randn([total], device=dev).mul_(sc), offs, N)
+        if grad:
+            live = torch.cat([l.noise_strength.to(torch.float32).reshape(1).expand(N * l.resolution * l.resolution) for l in self.layers])
+            self._cur = (torch.randn([total], device=dev) * live, offs, N)
+        else:
+            self._cur = (torch.randn([total], device=dev).mul_(sc), offs, N)
         return self
 
     def take(self, layer, N):
@@ -337,12 +345,17 @@ class ToRGBLayer(_CacheFree):
         weight, bias, d = self._parameters["weight"], self._parameters["bias"], self.__dict__
         if weight.shape[0] <= 96 and weight.shape[-1] == 1 and not d.get("mma_f16") and x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0:
             # the dedicated GEMM kernel (p3d_torgb_f32): the activation is read once, the skip image is added in the same launch
+            if torch.is_grad_enabled() and weight.requires_grad:  # under autograd: a recorded copy (the cached one stays as it is)
+                return ops.torgb(x, ops.torgb_weights(weight), weight.shape[0], styles, bias=bias, clamp=self.conv_clamp, skip=skip,
+                                 skip_filter=skip_filter)
             key = (weight.data_ptr(), weight._version)
             if d.get("_wt_key") != key or not memo.enabled():
                 self._wt, self._wt_key = ops.torgb_weights(weight.detach()), key
             return ops.torgb(x, d["_wt"], weight.shape[0], styles, bias=bias, clamp=self.conv_clamp, skip=skip, skip_filter=skip_filter)
         y = ops.modulated_conv2d(x, weight, styles, demodulate=False, bias=bias, act="linear", gain=1.0,
                                  clamp=self.conv_clamp, weight_f16=_f16_operand(self), saturated=_domain_flag(self, x.device))
+        if skip is not None and torch.is_grad_enabled() and (y.requires_grad or skip.requires_grad):
+            return ops.upsample2d(skip, skip_filter) + y  # (under autograd: the differentiable up-sampling; same values)
         return ops.upsample2d_add(skip, skip_filter, y) if skip is not None else y
 
 
@@ -454,6 +467,38 @@ class StylePlan:
         self._memo = (memo_of, memo_of._version, tuple(ws.shape), out) if memo_of is not None else None
         return out
 
+    def with_grad(self, ws):
+        """The plan's values (the no-grad call's bits: one GEMM + ops.demod_coefs) carrying the gradient of a float32 torch
+        restatement of the same [N,I] / [N,O] arithmetic: styles = (w_l @ (A * weight_gain)^T + b * bias_gain) * g and
+        d = rsqrt(styles^2 @ (sum over taps of W^2)^T + 1e-8).  Not memoised."""
+        dev = ws.device
+        key = tuple([(l.affine.weight.data_ptr(), l.affine.weight._version, l.affine.bias.data_ptr(), l.affine.bias._version,
+                      l.weight.data_ptr(), l.weight._version) for _, _, l, _ in self.entries]) + (dev,)
+        if key != self._key or not memo.enabled():
+            self._build(dev)
+            self._key = key
+            self._memo = None
+        with torch.no_grad():
+            vals = self._compute(ws.detach(), dev)
+        ws = ws.to(torch.float32)
+        out = {}
+        for bname, lname, layer, wi in self.entries:
+            st, dc = vals[bname][lname]
+            aff = layer.affine
+            w = aff.weight.to(torch.float32) * aff.weight_gain
+            b = aff.bias.to(torch.float32)
+            if aff.bias_gain != 1:
+                b = b * aff.bias_gain
+            s_t = torch.addmm(b.unsqueeze(0), ws[:, wi], w.t())
+            if isinstance(layer, ToRGBLayer):
+                s_t = s_t * float(layer.weight_gain)
+            st = _Attach.apply(st, s_t)
+            if dc is not None:
+                w2 = layer.weight.to(torch.float32).square().sum(dim=(2, 3))
+                dc = _Attach.apply(dc, (s_t.square() @ w2.t() + 1e-8).rsqrt())
+            out.setdefault(bname, {})[lname] = (st, dc)
+        return out
+
     def _compute(self, ws, dev):
         N, self.num_ws = ws.shape[0], ws.shape[1]
         idx, bias, gain, table, total_waves = self._for_n(N, dev)
@@ -469,6 +514,18 @@ class StylePlan:
             dc = d[o_off * N:(o_off + O) * N].view(N, O) if o_off is not None else None
             out.setdefault(bname, {})[lname] = (st, dc)
         return out
+
+
+class _Attach(torch.autograd.Function):
+    """value (computed without autograd) with the gradient of `surrogate` (the same quantity as recorded torch ops)."""
+
+    @staticmethod
+    def forward(ctx, value, surrogate):
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, g
 
 
 def plan_entries(named_blocks, block_w0):
@@ -506,7 +563,7 @@ class SynthesisBlock(torch.nn.Module):
         self.num_torgb += 1
 
     def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, update_emas=False, pre=None, x_image=None, next_styles=None,
-                need_x=True, **layer_kwargs):
+                need_x=True, grad=False, **layer_kwargs):
         """pre: {layer name: (styles, demod coefficients)} from a StylePlan (all affine layers of the network in one GEMM),
         or None: every layer runs its own affine like the reference (networks_stylegan2.py:342,377).
         x_image: x as the ops.ActImage the previous block's conv1 wrote for this block's conv0 (then x itself is not read by conv0);
@@ -528,10 +585,10 @@ class SynthesisBlock(torch.nn.Module):
             # conv0 hands conv1 its operand (activation image) when conv1 can stage from one and its styles / demodulation
             # coefficients are known up front (a StylePlan)
             p1 = pre.get("conv1")
-            img_ok = p1 is not None and p1[1] is not None and _takes_image(self.conv1, self.resolution) and self.conv1.in_channels % 8 == 0
+            img_ok = not grad and p1 is not None and p1[1] is not None and _takes_image(self.conv1, self.resolution) and self.conv1.in_channels % 8 == 0
             x0 = x_image if (x_image is not None and pre.get("conv0") is not None and pre["conv0"][1] is not None) else x.to(torch.float32)
             x = self.conv0(x0, next(w_iter), pre=pre.get("conv0"), next_styles=p1[0] if img_ok else None, **layer_kwargs)
-            rides = _torgb_rides(self, x, pre)
+            rides = None if grad else _torgb_rides(self, x, pre)
             if rides is not None:  # ToRGB's channel sums from conv1's epilogue, finished by one small launch
                 hand = next_styles if isinstance(x, ops.ActImage) else None
                 x, x_next, part = self.conv1(x, next(w_iter), pre=p1, next_styles=hand, rgb=rides, want_y=need_x or (next_styles is not None and hand is None),
@@ -555,6 +612,15 @@ class SynthesisBlock(torch.nn.Module):
         if next_styles is not None:
             return x, img, x_next
         return x, img
+
+
+def _edit_channels(x, c0, k, fn):
+    """x with channels [c0, c0 + k) replaced by fn(those channels), out of place (the conditioning under autograd)."""
+    parts = [x[:, :c0]] if c0 > 0 else []
+    parts.append(fn(x[:, c0:c0 + k]))
+    if c0 + k < x.shape[1]:
+        parts.append(x[:, c0 + k:])
+    return torch.cat(parts, dim=1) if len(parts) > 1 else parts[0].contiguous()
 
 
 def _pixel_unshuffle(t, f):
@@ -591,8 +657,8 @@ class SynthesisNetwork(_CacheFree):
     def _cond_prepared(self, key, tensors, make):
         """make() cached under `key` for exactly these tensor OBJECTS at their current versions (strong references are kept, so
         a hit can never be another tensor that reused an address)."""
-        if not memo.enabled():
-            return make()
+        if not memo.enabled() or (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)):
+            return make()  # (a term of tensors that require grad is recorded afresh on every call: never cached)
         cache = self.__dict__.setdefault("_cond_cache", {})
         hit = cache.get(key)
         if hit is not None and len(hit[0]) == len(tensors) and all(a is b and v == b._version for (a, v), b in zip(hit[0], tensors)):
@@ -626,34 +692,39 @@ class SynthesisNetwork(_CacheFree):
         self.__dict__.pop("_noise_pool", None)
         return super()._apply(fn)
 
-    def _condition(self, lvl, res, x, img, cond, cm, chonkadd, image_styles=None, flag=None):
+    def _condition(self, lvl, res, x, img, cond, cm, chonkadd, image_styles=None, flag=None, grad=False):
         """x, img: the block's FRESH outputs — owned by this call, written in place below.  (Inference only: under autograd, or if a
         caller ever aliased a block output, the in-place adds would be visible through the alias; the blocks return new tensors.)
         image_styles: the styles of the next block's conv0 when that layer stages from an activation image — where the level's only
         edit of x is ONE in-place add (the resnet chonk, `add_4`, `add_shuffle2_4`: the released model's modes) the add and the image
-        of the edited x come from one launch (ops.act_to_image_add) and the image is returned as the third value (else None)."""
-        x, img = self._condition_impl(lvl, res, x, img, cond, cm, chonkadd, image_styles, flag)
+        of the edited x come from one launch (ops.act_to_image_add) and the image is returned as the third value (else None).
+        grad: under autograd every edit is out of place (the same element-wise values, recorded)."""
+        x, img = self._condition_impl(lvl, res, x, img, cond, cm, chonkadd, image_styles, flag, grad)
         ximg = self.__dict__.pop("_cond_image", None)
         return x, img, ximg
 
-    def _add_to(self, x, t, c0, image_styles, flag, fuse):
-        """x[:, c0 : c0 + C_t] += t, with the next conv0's image from the same launch where asked for and possible."""
+    def _add_to(self, x, t, c0, image_styles, flag, fuse, grad=False):
+        """x[:, c0 : c0 + C_t] += t, with the next conv0's image from the same launch where asked for and possible; returns x.
+        grad: out of place."""
+        if grad:
+            return _edit_channels(x, c0, t.shape[1], lambda v: v + t)
         if fuse and image_styles is not None and x.is_contiguous() and x.dtype == torch.float32 and t.dtype == torch.float32 \
                 and c0 % 8 == 0 and t.shape[1] % 8 == 0 and x.shape[1] % 8 == 0 and t.shape[0] in (1, x.shape[0]) and tuple(t.shape[2:]) == tuple(x.shape[2:]):
             self.__dict__["_cond_image"] = ops.act_to_image_add(x, image_styles, t, c0, saturated=flag)
         else:
             x[:, c0:c0 + t.shape[1]].add_(t)
+        return x
 
-    def _condition_impl(self, lvl, res, x, img, cond, cm, chonkadd, image_styles, flag):
+    def _condition_impl(self, lvl, res, x, img, cond, cm, chonkadd, image_styles, flag, grad=False):
         self.__dict__.pop("_cond_image", None)
         if self.cond_mode == "none":
             return x, img
-        assert not (torch.is_grad_enabled() and (x.requires_grad or img.requires_grad)), "inference only: the conditioning is applied in place"
+        assert grad or not (torch.is_grad_enabled() and (x.requires_grad or img.requires_grad)), "the in-place conditioning is for calls without autograd"
         if res == 8 and chonkadd > 0:  # resnet "chonk" added to the first channels of the 8x8 activations (:554-560)
             k = chonkadd
             chonk = cond["resnet_chonk"]
             t = self._cond_prepared(("chonk", k), [chonk], lambda: chonk[:, :k].to(x.dtype).clone())  # (a copy: an address that outlives the subject)
-            self._add_to(x, t, 0, image_styles, flag, True)
+            x = self._add_to(x, t, 0, image_styles, flag, True, grad)
             return x, img
         interp = torch.nn.functional.interpolate
         if self.cond_mode.startswith("ortho_front."):
@@ -689,22 +760,30 @@ class SynthesisNetwork(_CacheFree):
             only_add = ("add_4" in cm) != ("add_shuffle2_4" in cm) and not ({"concatfront", "mult_shuffle2_4", "crossavg_4", "crossavgt_38"} & cm)
             if "add_4" in cm:
                 t = resized("add_4")
-                self._add_to(x, t, x.shape[1] - t.shape[1], image_styles, flag, only_add)
+                x = self._add_to(x, t, x.shape[1] - t.shape[1], image_styles, flag, only_add, grad)
             if "concatfront" in cm:
                 t = self._cond_prepared(("concatfront", lvl, tuple(x.shape[2:])), srcs,
                                         lambda: interp(self._cond_prepared("cimg", srcs, make_cimg), size=x.shape[-2:], mode="bilinear"))
-                x[:, -t.shape[1]:].copy_(t)
+                if grad:
+                    x = _edit_channels(x, x.shape[1] - t.shape[1], t.shape[1], lambda v: t.expand(v.shape))
+                else:
+                    x[:, -t.shape[1]:].copy_(t)
             if "add_shuffle2_4" in cm or "mult_shuffle2_4" in cm:
                 t = resized("shuffle2_4", unshuffle=not (lvl < len(self.block_resolutions) - 2))
                 if "add_shuffle2_4" in cm:
-                    self._add_to(x, t, x.shape[1] - t.shape[1], image_styles, flag, only_add)
+                    x = self._add_to(x, t, x.shape[1] - t.shape[1], image_styles, flag, only_add, grad)
+                elif grad:
+                    x = _edit_channels(x, x.shape[1] - t.shape[1], t.shape[1], lambda v: v * t)
                 else:
                     x[:, -t.shape[1]:].mul_(t)
             if "inj_6b_4" in cm and res == self.block_resolutions[-1]:
                 front = cond["image_ortho_front"]
                 t = self._cond_prepared(("inj_6b_4", tuple(img.shape[2:])), [front],
                                         lambda: interp((front.flip(dims=(-2,)) * 2 - 1) * 4, size=img.shape[-2:], mode="bilinear"))
-                img[:, :t.shape[1]].add_(t)
+                if grad:
+                    img = _edit_channels(img, 0, t.shape[1], lambda v: v + t)
+                else:
+                    img[:, :t.shape[1]].add_(t)
         if "crossavg_4" in cm:
             k = int(x.shape[1] // 8)
             h, v = x[:, 0:k], x[:, k:2 * k]
@@ -717,7 +796,19 @@ class SynthesisNetwork(_CacheFree):
                            t.permute(0, 1, 3, 2), x[:, 3 * k:]], dim=1)
         return x, img
 
+    def _records_grad(self, ws, cond, latent_injection):
+        """This call runs under autograd: grad mode is on and ws, a parameter, a latent injection or a conditioning tensor requires
+        grad.  Then every layer writes its fp32 result (no activation-image hand-overs: the same bits, CONV_IMG's equivalence), the
+        conditioning is applied out of place, and the HIP backward is recorded (ops.modulated_conv2d / ops.torgb)."""
+        if not torch.is_grad_enabled():
+            return False
+        if ws.requires_grad or any(p.requires_grad for p in self.parameters()):
+            return True
+        extra = list((latent_injection or {}).values()) + (list(cond.values()) if isinstance(cond, dict) else [])
+        return any(isinstance(t, torch.Tensor) and t.requires_grad for t in extra)
+
     def forward(self, ws, cond, latent_injection=None, stop_level=None, return_more=False, **block_kwargs):
+        grad = self._records_grad(ws, cond, latent_injection)
         ws = ws.to(torch.float32)
         block_ws, w_idx = [], 0
         for res in self.block_resolutions:  # a block's ToRGB shares the next block's first w (:534-537)
@@ -737,14 +828,15 @@ class SynthesisNetwork(_CacheFree):
                 w0 += getattr(self, f"b{res}").num_conv
             plan = StylePlan(plan_entries([(f"b{res}", getattr(self, f"b{res}")) for res in self.block_resolutions], starts))
             self.__dict__["_style_plan"] = plan
-        pre = plan(ws, memo_of=ws)  # every layer's styles + demodulation coefficients: one GEMM + three small launches
+        # every layer's styles + demodulation coefficients: one GEMM + three small launches (under autograd: the same values, recorded)
+        pre = plan.with_grad(ws) if grad else plan(ws, memo_of=ws)
         use_pool = self.__dict__.get("noise_pool")  # per-network override (None: the process default)
         if block_kwargs.get("noise_mode", "random") == "random" and (NOISE_POOL if use_pool is None else use_pool):  # all layers' random noise of this pass: two launches
             pool = self.__dict__.get("_noise_pool")
             if pool is None:
                 blocks = [getattr(self, f"b{res}") for res in self.block_resolutions]
                 pool = self.__dict__["_noise_pool"] = NoisePool([l for b in blocks for l in ([b.conv1] if b.in_channels == 0 else [b.conv0, b.conv1])])
-            block_kwargs["noise_pool"] = pool.draw(ws.shape[0], ws.device)
+            block_kwargs["noise_pool"] = pool.draw(ws.shape[0], ws.device, grad=grad)
         x_image = None
         for lvl, (res, cur_ws) in enumerate(zip(self.block_resolutions, block_ws)):
             # conv1 of this block writes its result also as the image the next block's conv0 stages from (no conversion pass in
@@ -752,13 +844,15 @@ class SynthesisNetwork(_CacheFree):
             nxt = getattr(self, f"b{self.block_resolutions[lvl + 1]}") if lvl + 1 < len(self.block_resolutions) else None
             injected = latent_injection is not None and f"da_{lvl}" in latent_injection
             x_untouched = self.cond_mode == "none" and not injected
-            ns_any = _next_conv0_styles(nxt, pre.get(f"b{self.block_resolutions[lvl + 1]}") if nxt is not None else None, res) if not injected else None
+            ns_any = _next_conv0_styles(nxt, pre.get(f"b{self.block_resolutions[lvl + 1]}") if nxt is not None else None, res) \
+                if not (injected or grad) else None
             ns = ns_any if x_untouched else None
-            out = getattr(self, f"b{res}")(x, img, cur_ws, pre=pre[f"b{res}"], x_image=x_image, next_styles=ns, **block_kwargs)
+            out = getattr(self, f"b{res}")(x, img, cur_ws, pre=pre[f"b{res}"], x_image=x_image, next_styles=ns, grad=grad, **block_kwargs)
             x, img, x_image = out if ns is not None else (out[0], out[1], None)
             # a conditioned level edits x between the blocks: the edit (where it is one in-place add) writes the next conv0's image itself
             x, img, cimg = self._condition(lvl, res, x, img, cond, cm, chonk, image_styles=None if x_untouched else ns_any,
-                                           flag=_domain_flag(nxt._modules["conv0"], x.device) if (nxt is not None and not x_untouched) else None)
+                                           flag=_domain_flag(nxt._modules["conv0"], x.device) if (nxt is not None and not x_untouched) else None,
+                                           grad=grad)
             if cimg is not None:
                 x_image = cimg
             x, img = x.contiguous(), img.contiguous()
