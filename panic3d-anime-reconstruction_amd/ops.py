@@ -956,7 +956,7 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, padding=0, resample_fi
                      next_styles=None, rgb_weight=None, rgb_styles=None, want_y=True):
     """modulated_conv2d (networks_stylegan2.py:40-97) FUSED with the bias_act that follows it in SynthesisLayer.forward
     (:350-352) / ToRGBLayer.forward (:379).  Supported shapes are the generator's: 3x3 / padding 1 / up 1 or 2, and 1x1.
-    noise: None, [H,W] (noise_const * strength) or [N,1,H,W] (random * strength).
+    noise: None, [H,W] / [1,1,H,W] (noise_const * strength, shared) or [N,1,H,W] (random * strength); other shapes raise.
     weight_f16 (from conv_weights_to_f16): run the matrix cores on f16 operands (fp32 accumulate, fp32 in/out) — what the
     reference's fp16 super-resolution blocks do on the GPU, with less rounding; needs I % 16 == 0.  A [2,O,k*k,I] tensor
     (conv_weights_to_f16(split=True)) selects the two-term variant: fp32-class results on the f16 matrix cores; `saturated`: an
@@ -1004,9 +1004,10 @@ def _modulated_conv2d_impl(x, weight, styles, noise=None, up=1, padding=0, resam
     nps = 0
     if noise is not None:
         noise = _chk(noise, "noise")
-        nps = 1 if noise.numel() == N * H * up * W * up and noise.ndim == 4 and N > 1 else 0
-        if noise.numel() not in (H * up * W * up, N * H * up * W * up):
-            raise RuntimeError("noise must be [H*up, W*up] or [N,1,H*up,W*up]")
+        # exactly the documented shapes: any other layout with N*H*W elements would be read as ONE shared map
+        if tuple(noise.shape) not in ((H * up, W * up), (1, 1, H * up, W * up), (N, 1, H * up, W * up)):
+            raise RuntimeError("noise must be [H*up, W*up], [1,1,H*up,W*up] or [N,1,H*up,W*up]")
+        nps = 1 if noise.shape[0] == N and noise.ndim == 4 and N > 1 else 0
     fir = None
     if up == 2:
         fir = prepared_filter(resample_filter, dev_, 4.0, False)  # upfirdn2d.py:193-196, gain = up^2
@@ -1266,7 +1267,6 @@ class _ModConvFn(torch.autograd.Function):
         gw = dw.view(ks, ks, O, I).permute(2, 3, 0, 1).contiguous()
         g_noise = None
         if want_noise:
-            ns = ctx.noise_shape
-            n_el = int(np.prod(ns))
-            g_noise = (gn if n_el == gn.numel() else gn.sum(0)).reshape(ns)
+            ns = ctx.noise_shape  # one of the forward's three shapes: per sample only as [N,1,H,W] with N > 1
+            g_noise = (gn if len(ns) == 4 and ns[0] == N and N > 1 else gn.sum(0)).reshape(ns)
         return (gx, gw, gs, (gd.view_as(dcoef) if gd is not None else None), (gb.sum(0) if bias is not None else None), g_noise, None)

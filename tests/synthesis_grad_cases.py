@@ -76,3 +76,70 @@ def check_against_fixture(net, ws, cond, inj, g, tol=1e-4):
         elif p.grad is not None and torch.count_nonzero(p.grad) > 0:
             bad.append((n, "non-zero gradient where the reference has none"))
     assert not bad, bad
+
+
+# ---- the kernel-level matrix of tests/test_hip_synthesis_grad_edges.py ------------------------------------------------------------
+# A designed covering list, not a product: every tail of the 64 x 64 GEMM tiles and 16-wide K chunks (1, 15/17, 63/65, 130), maps
+# that are non-square with pixel counts off multiples of 16 and 64, and every (taps, stride, pad) / index map the ABI documents.
+# tests/test_synthesis_grad_ref_cpu.py checks the gate at the largest K of each list.
+def _dgrad_cases():
+    """(N, Ci, Co, Hi, Wi, Ho, Wo, taps, stride, pad): Ci is the K-chunk tail, Co the row-tile tail."""
+    CI, CO = (1, 15, 16, 17, 33, 130), (1, 3, 63, 64, 65, 130)
+    MAPS = ((1, 1), (7, 13), (5, 67), (33, 33), (13, 7), (4, 9))
+    out, i = [], 0
+    for taps in (1, 9):
+        for stride in (1, 2):
+            for pad in (0, 1, 2):
+                for _ in range(3):
+                    Ho, Wo = MAPS[(i + i // 6) % 6]
+                    kt = 3 if taps == 9 else 1
+                    Hi = max(1, stride * (Ho - 1) + kt - 2 * pad + i % 3 - 1)
+                    Wi = max(1, stride * (Wo - 1) + kt - 2 * pad + (i + 1) % 3 - 1)
+                    out.append((3 if (i // 2) % 2 else 1, CI[i % 6], CO[(i + i // 6) % 6], Hi, Wi, Ho, Wo, taps, stride, pad))
+                    i += 1
+    # the product layers at 4^2 and 8^2: plain (flipped weights), up (stride 2 after the FIR adjoint), 1x1
+    out += [(1, 512, 512, 4, 4, 4, 4, 9, 1, 1), (3, 512, 512, 8, 8, 8, 8, 9, 1, 1), (1, 512, 512, 9, 9, 4, 4, 9, 2, 0),
+            (3, 512, 256, 17, 17, 8, 8, 9, 2, 0), (1, 96, 256, 8, 8, 8, 8, 1, 1, 0)]
+    return out
+
+
+DGRAD_CASES = _dgrad_cases()
+
+# index maps of p3d_conv_wgrad_f32: kind -> (taps, (sg, ag, pg), (sx, ax, px0), g map size, x map size) for a domain (Hd, Wd)
+WGRAD_MAPS = {
+    "plain": (9, (1, 0, 0), (1, 1, 1), lambda h, w: (h, w), lambda h, w: (h, w)),
+    "up": (9, (2, 1, 0), (1, 0, 0), lambda h, w: (2 * h + 1, 2 * w + 1), lambda h, w: (h, w)),
+    "1x1": (1, (1, 0, 0), (1, 0, 0), lambda h, w: (h, w), lambda h, w: (h, w)),
+    "pad2": (9, (1, 1, 2), (2, 1, 2), lambda h, w: (h + 1, w + 2), lambda h, w: (2 * h, 2 * w + 1)),  # not a product map
+    "step0": (9, (2, 0, 1), (1, 1, 0), lambda h, w: (2 * h, 2 * w), lambda h, w: (h + 2, w + 1)),
+}
+# (kind, N, O, I, Hd, Wd): O is the row-tile tail, I the column-tile tail, the domain the K of one sample (P < 16, P % 16 != 0,
+# several slabs with a ragged last one where O·I is small and the map large)
+_WG = [("plain", 1, 1, 1, 1, 1), ("plain", 3, 3, 17, 7, 13), ("plain", 1, 64, 64, 5, 67), ("plain", 3, 65, 63, 7, 13),
+       ("plain", 1, 130, 15, 16, 16), ("plain", 3, 17, 3, 63, 61), ("plain", 2, 1, 130, 33, 33), ("plain", 3, 15, 65, 3, 5),
+       ("up", 1, 3, 1, 2, 7), ("up", 3, 17, 64, 7, 13), ("up", 1, 63, 130, 4, 4), ("up", 3, 64, 17, 8, 8), ("up", 1, 3, 3, 33, 31),
+       ("up", 3, 130, 65, 5, 6),
+       ("1x1", 1, 1, 1, 1, 1), ("1x1", 3, 3, 96, 7, 13), ("1x1", 1, 96, 130, 5, 67), ("1x1", 3, 17, 15, 63, 61),
+       ("1x1", 1, 130, 130, 16, 16), ("1x1", 2, 65, 1, 3, 5), ("1x1", 1, 3, 17, 61, 67),
+       ("pad2", 1, 3, 17, 7, 13), ("pad2", 3, 64, 65, 5, 6), ("pad2", 1, 15, 1, 33, 33),
+       ("step0", 3, 17, 3, 7, 13), ("step0", 1, 65, 64, 4, 9), ("step0", 1, 1, 15, 63, 61),
+       # the product layers at 4^2 and 8^2
+       ("plain", 1, 512, 512, 4, 4), ("plain", 3, 512, 512, 8, 8), ("up", 1, 512, 512, 4, 4), ("up", 3, 256, 256, 8, 8)]
+# (case, with s, with g_d): s on two of every three, g_d on every sample-3 case and every other one besides
+WGRAD_CASES = [(c, i % 3 != 2, c[1] == 3 or i % 2 == 0) for i, c in enumerate(_WG)]
+
+# (N, C, HW)
+MOD_CASES = [(1, 1, 1), (3, 3, 7), (1, 17, 255), (3, 130, 256), (1, 15, 257), (3, 17, 4099), (1, 1, 4099), (3, 130, 1), (2, 65, 7),
+             (1, 512, 64)]
+
+# (N, C, HW, act, alpha, gain, clamp, dscale, g_out aliases g_y, want_noise)
+BIAS_ACT_CASES = [(1, 1, 1, 1, 0.2, float(np.sqrt(2)), None, False, False, True),
+                  (3, 15, 7, 1, 0.3, 1.7, None, True, False, True),
+                  (2, 17, 255, 0, 0.2, 1.0, 0.5, False, True, True),
+                  (3, 96, 257, 1, 0.1, 0.9, 0.75, True, True, True),
+                  (1, 96, 16, 1, 0.2, float(np.sqrt(2)), 256.0, True, False, True),
+                  (3, 1, 300, 0, 0.0, 2.5, 1.0, True, False, True),
+                  (1, 17, 4099, 1, 0.05, 1.3, 1.0, False, False, True),
+                  (3, 16, 5, 1, 0.25, 1.0, None, False, True, False),
+                  (1, 130, 33, 0, 0.0, 1.0, None, True, False, True),
+                  (3, 64, 64, 1, 0.2, float(np.sqrt(2)), 0.0, True, False, True)]

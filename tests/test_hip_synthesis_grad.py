@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 import p3d_testing as T
 import synthesis_grad_cases as SC
+import synthesis_grad_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -25,18 +26,8 @@ def P():
     return panic3d_amd
 
 
-def _fir64(f):
-    return (f.double() * 4.0).flip([0, 1])
-
-
-def _act_masked(z, y_ours, alpha, gain, clamp):
-    """clamp(lrelu(z) * gain) whose branch decisions (slope, clamp) are those of the kernel's output y_ours."""
-    pos = y_ours > 0
-    a = torch.where(pos, z, z * alpha) * gain
-    if clamp is not None:
-        keep = y_ours.abs() < clamp
-        a = torch.where(keep, a, a.detach().clamp(-clamp, clamp))
-    return a
+_fir64 = R.fir_ref
+_act_masked = R.act_masked  # clamp(lrelu(z) * gain) on the branch decisions (slope, clamp) of the kernel's output
 
 
 def _modconv64(x, w, s, d, b, noise, up, f, y_ours, clamp):
