@@ -176,6 +176,13 @@ int p3d_render_rng_f32(const float* planes_nhwc, int N, int H, int W, const floa
                        float* out_wsum, float* out_xyz, void* workspace, size_t workspace_bytes, const p3d_dumps* dumps,
                        void* stream);
 
+/* Which launch the three render entry points above make for these arguments (has_dumps: dumps != NULL; has_ray_limits: ray_start
+ * != NULL), so that a binding asks instead of restating the library's choice.  Writes cap >= 6 values to out, in this order:
+ * samples per wave-step (1: k_render, 32 rays per wave; 2 / 4: k_render_slots, 16 / 8 rays per wave), tiles (waves of work),
+ * wave-level decode steps with every sample decoded, grid, block, dynamic LDS bytes.  Returns 0, or the P3D_E_* code that
+ * p3d_render_limits_f32 returns for these arguments (with valid buffers); P3D_E_ARG for opts == NULL, out == NULL or cap < 6. */
+int p3d_render_plan_info(int N, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits, int64_t* out, int cap);
+
 /* sample_stratified (renderer.py:303-326, numeric ray_start/ray_end branch).  jitter, out [NR][S]. */
 int p3d_sample_stratified_f32(float ray_start, float ray_end, float depth_delta, int S, const float* jitter, int64_t NR,
                               float* out_depths, void* stream);

@@ -16,35 +16,15 @@
 #pragma once
 #include "p3d_math.hpp"
 #include "../../include/panic3d_hip.h"
+#include "p3d_lds_layout.hpp"
 
-// ---- LDS image of the decoder parameters (per workgroup), in MFMA operand order -------------------------------
-//   W0A [2][4][64][4] : tile t, s4, lane l, e  -> w0[32t + (l&31)][16(l>>5) + 4*s4 + e]
-//   W1A [2][4][64][4] : tile t, s4, lane l, e  -> w1[1 + (l&31)][nlo(t, 4*s4+e) + 4(l>>5)]
-//   B0P [2][2][16]    : half h, tile t, reg r  -> b0[32t + rowof(r) + 4h]
-//   B1P [2][16]       : half h, reg r          -> b1[1 + rowof(r) + 4h]
-//   W1S [2][32]       : half h, (t,s)          -> w1[0][nlo(t,s) + 4h]
-//   B1S [4]           : b1[0], 0, 0, 0
-// with rowof(r) = (r&3) + 8(r>>2) and nlo(t,s) = 32t + rowof(s).
-#define P3D_LDS_W0A 0
-#define P3D_LDS_W1A 2048
-#define P3D_LDS_B0P 4096
-#define P3D_LDS_B1P 4160
-#define P3D_LDS_W1S 4192
-#define P3D_LDS_B1S 4256
-#define P3D_LDS_MLP_FLOATS 4260
 #define P3D_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0)
 
 // ---- tolerance mode of the FINAL pass (P3D_FLAG_FAST_COLOR) --------------------------------------------
 // Both layers on v_mfma_f32_32x32x16_f16 (16x the f32 MFMA rate) with every operand split into two f16 terms
 // (x = xh + xl, xh = f16(x) by truncation, xl = f16(x - xh)): x*w ~ xh*wh + xl*wh + xh*wl, fp32 accumulation — about 2^-21
 // relative per product — and the activations on the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32).
-// Extra LDS image (only in the FAST kernels), in MFMA operand order, 16 B per lane:
-//   W0H [2 t][2 q][2 hi/lo][64 lanes][8 f16] : w0[32t + (l&31)][16(l>>5) + 8q + i]
-//   W1H [2 t][2 pp][2 hi/lo][64 lanes][8 f16]: w1[1 + (l&31)][32t + rowof(8pp + i) + 4(l>>5)]   (overlays W1A: the f32
-//                                               colour weights are never used by a FAST kernel)
-#define P3D_LDS_W0H P3D_LDS_MLP_FLOATS
-#define P3D_LDS_W1H P3D_LDS_W1A
-#define P3D_LDS_FAST_FLOATS (P3D_LDS_MLP_FLOATS + 2048)
+// Extra LDS image: W0H / W1H in p3d_lds_layout.hpp.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #define P3D_MFMA_H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)

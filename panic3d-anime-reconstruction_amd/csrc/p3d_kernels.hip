@@ -22,25 +22,13 @@
 #include <type_traits>
 
 #include "p3d_decode.hpp"
+#include "p3d_render_plan.hpp"
 
 #define P3D_WAVES_PER_WG 4
-#define P3D_RENDER_WAVES 4  // k_render workgroup (two workgroups per CU -> two waves per SIMD)
-// Quad-cooperative gathers (p3d_decode.hpp) in k_render: every decode of both kernels (measured with the 76-instruction transpose,
+// Quad-cooperative gathers (p3d_decode.hpp) in every decode of k_render and k_render_slots (measured with the 76-instruction transpose,
 // 512^2 x (48+48), canonical / surface ms: tolerance kernel 1.99 / 2.62 -> 1.61 / 2.13 with them in the final AND the coarse pass
 // (final only: 1.78 / 2.22); exact kernel 2.32 / 3.33 -> 1.93 / 3.09 (final only 2.09 / 3.16); every sample decoded 3.39 / 5.16).
 // Not in the exact point / grid query (density-only decoder: 12.75 vs 12.65 ms at 512^3); yes in the tolerance one (10.2 -> 7.7).
-#ifndef P3D_QUAD_COARSE
-#define P3D_QUAD_COARSE 1
-#endif
-#ifndef P3D_QUAD_EXACT
-#define P3D_QUAD_EXACT 1
-#endif
-#ifndef P3D_QUAD_PAIR
-#define P3D_QUAD_PAIR 1     // ... and in the small-launch kernel k_render_slots
-#endif
-#ifndef P3D_RENDER_OCC
-#define P3D_RENDER_OCC 2    // waves per SIMD the register allocation of k_render is held to (launch_bounds) and the host packs for
-#endif
 #define P3D_WG (64 * P3D_WAVES_PER_WG)
 
 // =====================================================================================================================
@@ -445,7 +433,7 @@ P3D_DEV void p3d_inverse_cdf(const float* cdfA, TCF tc, int Ns, int j, const flo
 //   In the final pass a skipped sample's colour is needed only if one of its two interval weights is non-zero (sigma of
 //   the neighbour >= ~794); that is checked on the exact weights and, if it ever happens, the sample is decoded after
 //   all — results are bit-identical by construction.
-// the host picks the workgroup size (1, 2 or 4 waves) that fills the CU's 160 KB of LDS best
+// the plan (p3d_render_plan.hpp) picks the workgroup size (1, 2 or 4 waves) that fills the CU's 160 KB of LDS best
 // FAST (P3D_FLAG_FAST_COLOR): the FINAL pass decodes in tolerance mode (p3d_decode_wave_fast); the coarse pass, and with it
 // the importance resampling (inverse-CDF indices, fine depths, merged depth order), stays on the exact contract.
 // EARLY: the exact early-outs (compile-time, so that the measurement / dump variant is the plain uniform loop).
@@ -460,15 +448,13 @@ P3D_DEV void p3d_inverse_cdf(const float* cdfA, TCF tc, int Ns, int j, const flo
 // torch.rand_like produces it, the stratified depths can be out of order only between NEIGHBOURS (rounding), which the sorted
 // accessor resolves with two more reads; any other disorder takes an exact O(Sc^2) selection (tc_sorted below).
 #define P3D_NF_EXACT(NF) ((NF) == 48 || (NF) == 96)
-#define P3D_TCG(NF, DUMP, EARLY) ((NF) == 96 && (EARLY) && !(DUMP))
-#define P3D_NF_OCC(NF, TCGV) (((NF) >= 96 && !(TCGV)) ? 1 : P3D_RENDER_OCC)
-// TCG is a template parameter of its own (default: on wherever it can be): the host turns it OFF for the launches whose coarse
+// TCG is a template parameter of its own (default: on wherever it can be): the plan turns it OFF for the launches whose coarse
 // depths are not the plain stratified spacing — per-ray limits (ray_start = 'auto') and disparity spacing — which depth_of() below
 // does not know (with TCG derived from (NF, DUMP, EARLY) alone those launches silently rendered the fixed spacing).
-template <int NF, bool DUMP, bool FAST, bool EARLY, bool TCG = P3D_TCG(NF, DUMP, EARLY)>
-__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_render(RenderParams p) {
+template <int NF, bool DUMP, bool FAST, bool EARLY, bool TCG = p3d_render_tcg(NF, DUMP, EARLY)>
+__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) void k_render(RenderParams p) {
     static_assert(!(DUMP && EARLY), "dumps need every sample decoded");
-    static_assert(!TCG || P3D_TCG(NF, DUMP, EARLY), "TCG exists only for the production 96-key kernel");
+    static_assert(!TCG || p3d_render_tcg(NF, DUMP, EARLY), "TCG exists only for the production 96-key kernel");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     p3d_load_mlp_to_lds(lds, p.w0, p.b0, p.w1, p.b1, !FAST);
     if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
@@ -663,7 +649,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
                     const bool skip = __builtin_amdgcn_ballot_w64(live) == 0;
                     if (!skip) {
                         f32x16 dummy;
-                        p3d_decode_wave<false, (FAST || P3D_QUAD_EXACT != 0) && (P3D_QUAD_COARSE != 0)>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
+                        p3d_decode_wave<false, true>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
                     }
                     mword |= (cropped || (live && sigma == P3D_SIGMA_MASKED)) ? (1u << (i & 31)) : 0u;
                     if ((i & 31) == 31 || i == Sc - 1) {  // wave-uniform
@@ -691,7 +677,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
             }
             if (!skip) {
                 f32x16 dummy;
-                p3d_decode_wave<false, (FAST || P3D_QUAD_EXACT != 0) && (P3D_QUAD_COARSE != 0)>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
+                p3d_decode_wave<false, true>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
             }
             if (early) {  // a lane whose gathers were suppressed (dead ray) decoded garbage: its sample is NOT known to be masked
                 mword |= (cropped || (live && sigma == P3D_SIGMA_MASKED)) ? (1u << (i & 31)) : 0u;
@@ -990,7 +976,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, P3D_NF_OCC(NF, TCG)) void k_
             if (__builtin_amdgcn_ballot_w64(live) != 0) {
                 bool have_rgb;  // EARLY: colour on demand (p3d_decode.hpp, LAZY): a step whose live samples are all masked has none
                 if constexpr (FAST) have_rgb = p3d_decode_wave_fast<true, true, EARLY, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
-                else have_rgb = p3d_decode_wave<true, P3D_QUAD_EXACT != 0, EARLY>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
+                else have_rgb = p3d_decode_wave<true, true, EARLY>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
                 if constexpr (!DUMP) ndec += 1;
                 skipped = !live || !have_rgb;  // per lane: a lane whose gathers were suppressed has no colour
                 if (known) sigma = P3D_SIGMA_MASKED;
@@ -1129,7 +1115,7 @@ P3D_DEV float p3d_select(const float (&x)[N], int k) {
 // waves).  The EXACT four-slot ones under the 256-register cap spilled 108-127 VGPRs (164-176 B of scratch per lane, round 4), and
 // the host picks them only for launches of <= 8192 rays = <= 1024 waves — one per SIMD whatever the cap.
 template <int SLOTS, int NF, bool FAST, bool WO = false>
-__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, (SLOTS == 4 && FAST) ? 2 : 1) void k_render_slots(RenderParams p) {
+__global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, FAST)) void k_render_slots(RenderParams p) {
     static_assert(SLOTS == 2 || SLOTS == 4, "16 rays x 2 slots or 8 rays x 4 slots per wave");
     static_assert(!WO || (FAST && SLOTS == 4), "the weights-only launch exists for the tolerance mode (the renderer class's default, what the paste runs)");
     constexpr int RPW = 32 / SLOTS;  // rays per wave
@@ -1242,7 +1228,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, (SLOTS == 4 && FAST) ? 2 : 1
             }
             if (!skip) {
                 f32x16 dummy;
-                p3d_decode_wave<false, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
+                p3d_decode_wave<false, true>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
                 ndec += 1;
             }
             const Slots sx = exchange(sigma);
@@ -1352,14 +1338,14 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, (SLOTS == 4 && FAST) ? 2 : 1
                     if (__builtin_amdgcn_ballot_w64(prev_skipped && w != 0.0f) != 0) {
                         float s2;
                         f32x16 c2;
-                        if constexpr (FAST) p3d_decode_wave_fast<true, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
+                        if constexpr (FAST) p3d_decode_wave_fast<true, true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
                         else p3d_decode_wave<true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
                         if (prev_skipped) prev_rgb = c2;
                         prev_skipped = false;
                     }
                     if (__builtin_amdgcn_ballot_w64(skipped && w != 0.0f) != 0) {
                         float s2;
-                        if constexpr (FAST) p3d_decode_wave_fast<true, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, s2, rgb);
+                        if constexpr (FAST) p3d_decode_wave_fast<true, true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
                         else p3d_decode_wave<true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
                         skipped = false;
                     }
@@ -1399,8 +1385,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, (SLOTS == 4 && FAST) ? 2 : 1
                 skipped = __builtin_amdgcn_ballot_w64(live) == 0;
             }
             if (!skipped) {
-                if constexpr (FAST) p3d_decode_wave_fast<!WO, P3D_QUAD_PAIR != 0, false, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
-                else p3d_decode_wave<true, P3D_QUAD_PAIR != 0>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
+                if constexpr (FAST) p3d_decode_wave_fast<!WO, true, false, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
+                else p3d_decode_wave<true, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
                 ndec += 1;
                 skipped = !live;
             }
@@ -1859,7 +1845,17 @@ int p3d_decode_features_f32(const float* feats, int N, int64_t M, const float* w
 
 size_t p3d_render_workspace_bytes(int N, int64_t R, int Sc, int Sf) {
     (void)R; (void)Sc; (void)Sf;
-    return 256 + (size_t)(N > 0 ? N : 0) * 8;  // global min / max + decode-step count, then one min / max pair per view
+    return p3d_render_plan_workspace_bytes(N);
+}
+
+int p3d_render_plan_info(int N, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits, int64_t* out, int cap) {
+    if (!opts) return P3D_E_ARG;
+    const RenderPlan pl = p3d_render_plan(N, R, ray_tile_w, *opts, has_dumps != 0, has_ray_limits != 0);
+    if (pl.err) return pl.err;
+    if (!out || cap < 6) return P3D_E_ARG;
+    const int64_t info[6] = {pl.slots, pl.ntiles, pl.decode_steps_full, pl.grid, pl.block, (int64_t)pl.lds_bytes};
+    for (int i = 0; i < 6; ++i) out[i] = info[i];
+    return P3D_OK;
 }
 
 int p3d_render_f32(const float* planes, int N, int H, int W, const float* rays_o, const float* rays_d, int64_t R,
@@ -1907,10 +1903,11 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     if (Sc < 4 || Sc > P3D_MAX_S || Sf < 0 || Sf > P3D_MAX_S) return P3D_E_RANGE;
     if (Sf > 0 && !u && !rng) return P3D_E_ARG;
     if (H <= 0 || W <= 0 || (long long)H * W * 128 * 3 >= 0x7ffffff0LL) return P3D_E_RANGE;
-    if (workspace_bytes < p3d_render_workspace_bytes(N, R, Sc, Sf)) return P3D_E_WORKSPACE;
+    if (workspace_bytes < p3d_render_plan_workspace_bytes(N)) return P3D_E_WORKSPACE;
+    const RenderPlan pl = p3d_render_plan(N, R, ray_tile_w, *opts, dumps != nullptr, ray_start != nullptr);
+    if (pl.err) return pl.err;
     hipStream_t st = (hipStream_t)stream;
     RenderParams p;
-    p.blocked = 0;
     p.planes = planes; p.rays_o = rays_o; p.rays_d = rays_d; p.jitter = jitter; p.u = u;
     p.rng = rng; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
     p.w0 = w0; p.b0 = b0; p.w1 = w1; p.b1 = b1;
@@ -1922,131 +1919,34 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     p.ray_start = opts->ray_start; p.ray_end = opts->ray_end; p.depth_delta = opts->depth_delta;
     p.ray_start_arr = ray_start; p.ray_end_arr = ray_end;
     p.disparity = (opts->flags & P3D_FLAG_DISPARITY) ? 1 : 0;
-    if (p.disparity && ray_start) return P3D_E_RANGE;  // not with per-ray limits
     p.white_back = (opts->flags & P3D_FLAG_WHITE_BACK) ? 1 : 0;
     p.cfg = make_cfg(opts);
-    if (ray_tile_w > 0 && R % ray_tile_w == 0 && ray_tile_w % 8 == 0 && (R / ray_tile_w) % 4 == 0) {
-        p.tile_w = ray_tile_w;
-        p.tiles_x = ray_tile_w / 8;
-        p.tiles_per_img = (long long)p.tiles_x * (R / ray_tile_w / 4);
-    } else {
-        p.tile_w = 0;
-        p.tiles_x = 0;
-        p.tiles_per_img = (R + 31) / 32;
-    }
-    p.ntiles = p.tiles_per_img * N;
-    // per-wave LDS rows: tc (Sc) + wc/cdf/sorted-fine (max(Sc,Sf)) [+ tf (Sf) on the generic path]
-    // register-resident fine depths: 48 / 96 exactly (the trainer's and the eval-faithful rates), any other Sf <= 64 padded to 64;
-    // the rest sorts in LDS
-    const int nf = (Sf == 48) ? 48 : (Sf == 96 && Sc <= 96) ? 96 : (Sf <= 64 ? 64 : 0);
-    const bool dmp = dumps != nullptr;
-    const bool pair = !dmp && !(opts->flags & P3D_FLAG_NO_PAIR) && p.ntiles <= 512;  // (the small-launch kernel, below)
-    // the production 96-key kernel keeps no coarse-depth rows (P3D_TCG) and runs two waves per SIMD like the others
-    // (for the plain stratified spacing: per-ray limits and disparity spacing keep the LDS-resident 96-key kernel)
-    const bool tcg = nf == 96 && !dmp && !pair && !(opts->flags & P3D_FLAG_NO_EARLY_OUT) && !ray_start && !p.disparity;
-    const int occ = (nf >= 96 && !tcg) ? 1 : P3D_RENDER_OCC;  // waves per SIMD the instantiation is compiled for (P3D_NF_OCC)
-    // + two bit rows over the merged list (is-coarse / known-masked) + the known-masked bits of the coarse samples
-    p.lds_rows = Sc + (Sc > Sf ? Sc : Sf) + (nf == 0 ? Sf : 0) + 2 * ((Sc + Sf + 31) >> 5) + ((Sc + 31) >> 5);
-    if (tcg) p.lds_rows = (Sc > Sf ? Sc : Sf) + 2 * ((Sc + Sf + 31) >> 5);
-    int nwaves = P3D_RENDER_WAVES;
-    // small ray counts (e.g. the pipeline's 128^2 rays = 512 tiles): shrink the workgroup so that every CU gets work
-    while (nwaves > 1 && p.ntiles / nwaves < 2 * 256) nwaves >>= 1;
-    size_t lds_bytes;
-    const bool fast = (opts->flags & P3D_FLAG_FAST_COLOR) != 0 && Sf > 0;
-    const size_t lds_fixed = (size_t)((fast ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4) * 4, lds_wave = (size_t)p.lds_rows * 128;
-    if (nwaves == P3D_RENDER_WAVES) {
-        // large launch: the workgroup shape (4, 2 or 1 waves, as many workgroups as fit) that puts most waves on a CU, at
-        // most 8 (two per SIMD: the register cap); ties go to the LARGER workgroup.  48+48: 2 x 4 waves; 64+64: 3 x 2 instead of
-        // 1 x 4 (measured 6.85 -> 6.53 ms at 512^2); 96+96: 2 x 4 with the production kernel (no coarse-depth rows: P3D_TCG), 1 x 4
-        // with the LDS-resident instantiations (measured there: 2 x 2 waves 13.3 ms, 1 x 5 12.6, 1 x 4 11.2)
-        int best = 0, best_waves = 0;
-        for (int w = 4; w >= 1; w >>= 1) {
-            const size_t per_wg = lds_fixed + w * lds_wave;
-            if (per_wg > 160 * 1024) continue;
-            int wgs = (int)((160 * 1024) / per_wg);
-            int waves = wgs * w > 4 * occ ? 4 * occ / w * w : wgs * w;
-            if (waves > best_waves) { best_waves = waves; best = w; }
-        }
-        if (best == 0) return P3D_E_RANGE;
-        nwaves = best;
-    }
-    for (;; nwaves >>= 1) {
-        lds_bytes = lds_fixed + (size_t)nwaves * lds_wave;
-        if (lds_bytes <= 160 * 1024) break;
-        if (nwaves == 1) return P3D_E_RANGE;
-    }
+    p.tile_w = pl.tile_w; p.tiles_x = pl.tiles_x; p.tiles_per_img = pl.tiles_per_img; p.ntiles = pl.ntiles;
+    p.lds_rows = pl.lds_rows; p.swz = pl.swz; p.blocked = pl.blocked;
     hipLaunchKernelGGL(k_minmax_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, p.gminmax, p.per_view_clamp ? N : 0);
-    // small launches: 16 rays x 2 samples per wave (k_render_slots<2, ...>) while its waves still fit in ONE round on the 1024 SIMDs
-    // (measured at 48+48: 128^2 rays 0.74 -> 0.49 ms, but 192^2 = 1152 tiles 0.99 -> 1.28 ms: its steps are ~30 % dearer)
-    // ... and of those, 8 rays x 4 samples per wave (k_render_slots<4, ...>) where it measured faster (profiles/r04_notes.txt): launches of at
-    // most 8192 rays — fewer 16-ray waves than SIMDs: 64^2 x (96+96) 0.80 -> 0.60 ms exact, 0.60 -> 0.45 tolerance — and the
-    // tolerance mode at 96+96 (128^2: 0.63 -> 0.57 ms).  NOT the 128^2 exact launches (0.80 -> 0.88 at 96+96, 0.44 -> 0.49 at 48+48):
-    // a decode step is ~4k MFMA clocks + ~1.5k VALU instructions of ISSUE, which ONE wave per SIMD already saturates; a second wave
-    // per SIMD has nothing to hide and the per-ray work (draws, sort, marcher) is then done by twice as many waves.
-    // P3D_FLAG_QUAD8 / P3D_FLAG_PAIR16 force one of the two (tests, A/B timing).
-    // Round 5 (profiles/r05_notes.txt): the tolerance-mode quad kernels spill 30 VGPRs instead of 109 (the fold no longer copies its
-    // partial sums) and win at every sample count of a 128^2 view (48+48: 0.42 -> 0.325 ms vs 0.354 for the pair kernel; 96+96: 0.559 vs
-    // 0.618): the tolerance mode takes the quad kernel for every small launch.  The exact quad kernels are compiled for one wave per
-    // SIMD (no spills: 64^2 x (96+96) 0.60 -> 0.50 ms) and stay the choice for <= 8192 rays only.
-    const bool quad = pair && !(opts->flags & P3D_FLAG_PAIR16) &&
-                      ((opts->flags & P3D_FLAG_QUAD8) || (long long)N * R <= 8192 || (fast && (nf == 96 || nf == 48)));
-    dim3 grid, blk;
     auto launch = [&](void (*kernel)(RenderParams)) {
-        hipError_t e = p3d_ensure_dynamic_lds(kernel, lds_bytes);
+        hipError_t e = p3d_ensure_dynamic_lds(kernel, pl.lds_bytes);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(kernel, grid, blk, lds_bytes, st, p);
+        hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(pl.block), pl.lds_bytes, st, p);
         return p3d_check_launch();
     };
-    int rc;
-    if (pair) {
-        const int rpw = quad ? 8 : 16;  // rays per wave: 32 / sample slots
-        if (p.tile_w > 0) { p.tiles_x = ray_tile_w / 4; p.tiles_per_img = (long long)p.tiles_x * (R / ray_tile_w / (rpw / 4)); }
-        else p.tiles_per_img = (R + rpw - 1) / rpw;
-        p.ntiles = p.tiles_per_img * N;
-        const int wgs = quad ? 2 : 1;  // workgroups per CU the LDS should fit: two for the four-slot form
-        for (nwaves = P3D_RENDER_WAVES;; nwaves >>= 1) {
-            lds_bytes = lds_fixed + (size_t)nwaves * p.lds_rows * rpw * 4;  // rows of rpw rays
-            if (wgs * lds_bytes <= 160 * 1024) break;
-            if (nwaves == 1) { if (lds_bytes <= 160 * 1024) break; return P3D_E_RANGE; }
-        }
-        grid = dim3((unsigned)((p.ntiles + nwaves - 1) / nwaves));
-        blk = dim3(64 * nwaves);
-        // P3D_FLAG_WEIGHTS_ONLY: honoured by the tolerance-mode four-slot kernels at 48 / 96 fine samples (what paste_front's occlusion pass runs)
-        const bool wo = quad && fast && (opts->flags & P3D_FLAG_WEIGHTS_ONLY) != 0;
-        rc = p3d_with_nf(nf, [&](auto nfc) {
-            constexpr int NF = decltype(nfc)::value;
-            if constexpr (NF == 48 || NF == 96)
-                if (wo) return launch(k_render_slots<4, NF, true, true>);
-            if (quad) return launch(fast ? k_render_slots<4, NF, true> : k_render_slots<4, NF, false>);
-            return launch(fast ? k_render_slots<2, NF, true> : k_render_slots<2, NF, false>);
-        });
-    } else {
-        p.swz = 16;  // measured: 8..64 within 0.5 %, 1..4 and >= 256 about 1-3 % slower
-        p.blocked = 0;
-        {   // blocked tile order (k_render): whole 16 x 16-tile super-tiles per XCD run when the tile grid divides into them
-            static const int tile_order = getenv("P3D_TILE_ORDER") ? atoi(getenv("P3D_TILE_ORDER")) : 1;  // 0: row-major (A/B runs)
-            const long long tiles_y = p.tile_w > 0 ? p.tiles_per_img / p.tiles_x : 0;
-            // ... and into a multiple of 8 of them: 384^2 (18 super-tiles on 8 XCDs) loses 2-3 % to the imbalance, every shape with whole
-            // super-tiles per XCD is equal or up to 3 % better (profiles/r05_tile_order_shapes.json)
-            if (tile_order == 1 && p.tile_w > 0 && p.tiles_x % 16 == 0 && tiles_y % 16 == 0 && 256 % nwaves == 0 && (p.ntiles / 256) % 8 == 0) {
-                p.blocked = 1;
-                p.swz = 256 / nwaves;
+    const int rc = p3d_with_nf(pl.nf, [&](auto nfc) {
+        constexpr int NF = decltype(nfc)::value;
+        if constexpr (NF == 48 || NF == 96)
+            if (pl.kernel == RenderKernel::SLOTS4_WO) return launch(k_render_slots<4, NF, true, true>);
+        auto mode = [&](auto fc) {
+            constexpr bool F = decltype(fc)::value;
+            switch (pl.kernel) {
+            case RenderKernel::DUMP: return launch(k_render<NF, true, F, false>);
+            case RenderKernel::PLAIN: return launch(k_render<NF, false, F, false>);
+            case RenderKernel::EARLY_TCG: return launch(k_render<NF, false, F, true>);  // (NF == 96 only: the default TCG of that instantiation)
+            case RenderKernel::EARLY: return launch(k_render<NF, false, F, true, false>);
+            case RenderKernel::SLOTS2: return launch(k_render_slots<2, NF, F>);
+            default: return launch(k_render_slots<4, NF, F>);  // SLOTS4 (SLOTS4_WO at NF = 48 / 96: above)
             }
-        }
-        grid = dim3((unsigned)((p.ntiles + nwaves - 1) / nwaves));
-        blk = dim3(64 * nwaves);
-        rc = p3d_with_nf(nf, [&](auto nfc) {
-            constexpr int NF = decltype(nfc)::value;
-            auto mode = [&](auto fc) {
-                constexpr bool F = decltype(fc)::value;
-                if (dmp) return launch(k_render<NF, true, F, false>);
-                if (opts->flags & P3D_FLAG_NO_EARLY_OUT) return launch(k_render<NF, false, F, false>);
-                if (tcg) return launch(k_render<NF, false, F, true>);  // (NF == 96 only: the default TCG of that instantiation)
-                return launch(k_render<NF, false, F, true, false>);   // per-ray limits / disparity spacing at 96+96: the LDS-resident coarse column
-            };
-            return fast ? mode(std::true_type()) : mode(std::false_type());
-        });
-    }
+        };
+        return pl.fast ? mode(std::true_type()) : mode(std::false_type());
+    });
     if (rc) return rc;
     long long NR = (long long)N * R;
     hipLaunchKernelGGL(k_render_finish, dim3((unsigned)((NR + 255) / 256)), dim3(256), 0, st, out_depth, NR, p.gminmax,

@@ -1,0 +1,161 @@
+// p3d_render_plan.hpp — which kernel runs one render launch (render_impl, p3d_kernels.hip) and in what shape, decided in ONE place:
+// the instantiation, the ray tiles, the per-wave LDS rows, the workgroup size, the grid, the dynamic LDS and k_render's XCD tile
+// order.  Host code only (no HIP headers): tests/test_render_plan.py compiles it into a plain host program.
+//   p3d_render_tcg / p3d_render_occ / p3d_render_slots_occ   per-instantiation rules, shared with the kernels' template defaults
+//                                                            and __launch_bounds__
+//   p3d_render_plan              the plan of one launch: a pure function of its shape and options
+//   p3d_render_plan_workspace_bytes   what p3d_render_workspace_bytes answers
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/panic3d_hip.h"
+#include "p3d_lds_layout.hpp"
+
+#define P3D_RENDER_WAVES 4           // the widest render workgroup
+#define P3D_RENDER_LDS_CU (160 * 1024)  // LDS bytes of a CU
+
+// TCG ("coarse depths from global", see k_render): the default of k_render's TCG parameter — on wherever it can be
+constexpr bool p3d_render_tcg(int NF, bool DUMP, bool EARLY) { return NF == 96 && EARLY && !DUMP; }
+// waves per SIMD that k_render<NF, ..., TCG>'s registers are held to (__launch_bounds__) and the plan packs its LDS for: one for the
+// LDS-resident 96-key instantiations, two for every other
+constexpr int p3d_render_occ(int NF, bool TCG) { return (NF >= 96 && !TCG) ? 1 : 2; }
+// ... and k_render_slots<SLOTS, NF, FAST>'s: two for the four-slot tolerance-mode ones, one for the others (see that kernel)
+constexpr int p3d_render_slots_occ(int SLOTS, bool FAST) { return (SLOTS == 4 && FAST) ? 2 : 1; }
+
+enum class RenderKernel {
+    DUMP,       // k_render<NF, true, FAST, false>: every sample decoded, the stages dumped
+    PLAIN,      // k_render<NF, false, FAST, false>: every sample decoded (P3D_FLAG_NO_EARLY_OUT)
+    EARLY,      // k_render<NF, false, FAST, true, false>: the exact early-outs, coarse depths in LDS
+    EARLY_TCG,  // k_render<96, false, FAST, true, true>: the production 96-key kernel (coarse depths recomputed)
+    SLOTS2,     // k_render_slots<2, NF, FAST>: small launches, 16 rays x 2 samples per wave
+    SLOTS4,     // k_render_slots<4, NF, FAST>: small launches, 8 rays x 4 samples per wave
+    SLOTS4_WO,  // k_render_slots<4, NF, true, true>: ... weights only (NF = 48 / 96)
+};
+
+struct RenderPlan {
+    int err;              // P3D_OK, or the P3D_E_* code the render entry points return for these arguments (nothing else is set)
+    RenderKernel kernel;
+    int nf;               // the instantiation's fine-depth capacity: 48, 64, 96, or 0 (the generic path)
+    bool fast;            // FAST: the final pass in tolerance mode
+    int slots;            // samples per wave-step: 1 (k_render), 2 or 4 (k_render_slots)
+    int rays_per_wave;    // 32 / slots: the rays of one tile
+    int tile_w, tiles_x;  // tile_w > 0: screen tiles over a tile_w-wide image, tiles_x of them per row; 0: runs of rays_per_wave rays
+    long long tiles_per_img, ntiles;
+    int lds_rows;         // per-wave LDS rows of rays_per_wave floats
+    int nwaves;           // waves per workgroup
+    unsigned grid, block;
+    size_t lds_bytes;     // dynamic LDS per workgroup
+    int swz, blocked;     // k_render's XCD tile order (see the kernel); 0 for k_render_slots
+    long long decode_steps_full;  // wave-level decode steps with every sample decoded
+};
+
+static inline size_t p3d_render_plan_workspace_bytes(int N) {
+    return 256 + (size_t)(N > 0 ? N : 0) * 8;  // global min / max + decode-step count, then one min / max pair per view
+}
+
+static inline RenderPlan p3d_render_plan(int N, int64_t R, int ray_tile_w, const p3d_opts& o, bool has_dumps, bool has_ray_limits) {
+    RenderPlan pl = {};
+    const int Sc = o.Sc, Sf = o.Sf, flags = o.flags;
+    const bool disparity = (flags & P3D_FLAG_DISPARITY) != 0;
+    if (N <= 0 || R <= 0) pl.err = P3D_E_ARG;
+    else if (Sc < 4 || Sc > P3D_MAX_S || Sf < 0 || Sf > P3D_MAX_S) pl.err = P3D_E_RANGE;
+    else if (disparity && has_ray_limits) pl.err = P3D_E_RANGE;  // not with per-ray limits
+    if (pl.err) return pl;
+
+    // register-resident fine depths: 48 / 96 exactly (the trainer's and the eval-faithful rates), any other Sf <= 64 padded to 64;
+    // the rest sorts in LDS
+    pl.nf = (Sf == 48) ? 48 : (Sf == 96 && Sc <= 96) ? 96 : (Sf <= 64 ? 64 : 0);
+    pl.fast = (flags & P3D_FLAG_FAST_COLOR) != 0 && Sf > 0;
+    const bool tiled = ray_tile_w > 0 && R % ray_tile_w == 0 && ray_tile_w % 8 == 0 && (R / ray_tile_w) % 4 == 0;
+    const auto tile = [&](int rpw) {  // k_render: 8 x 4-ray screen tiles; k_render_slots: 4 x (rpw / 4)
+        const int tw = rpw == 32 ? 8 : 4;
+        pl.rays_per_wave = rpw;
+        pl.tile_w = tiled ? ray_tile_w : 0;
+        pl.tiles_x = tiled ? ray_tile_w / tw : 0;
+        pl.tiles_per_img = tiled ? (long long)pl.tiles_x * (R / ray_tile_w / (rpw / tw)) : (R + rpw - 1) / rpw;
+        pl.ntiles = pl.tiles_per_img * N;
+    };
+    tile(32);
+
+    // small launches: 16 rays x 2 samples per wave (k_render_slots<2, ...>) while its waves still fit in ONE round on the 1024 SIMDs
+    // (measured at 48+48: 128^2 rays 0.74 -> 0.49 ms, but 192^2 = 1152 tiles 0.99 -> 1.28 ms: its steps are ~30 % dearer)
+    // ... and of those, 8 rays x 4 samples per wave (k_render_slots<4, ...>) where it measured faster (profiles/r04_notes.txt): launches of at
+    // most 8192 rays — fewer 16-ray waves than SIMDs: 64^2 x (96+96) 0.80 -> 0.60 ms exact, 0.60 -> 0.45 tolerance — and the
+    // tolerance mode at 96+96 (128^2: 0.63 -> 0.57 ms).  NOT the 128^2 exact launches (0.80 -> 0.88 at 96+96, 0.44 -> 0.49 at 48+48):
+    // a decode step is ~4k MFMA clocks + ~1.5k VALU instructions of ISSUE, which ONE wave per SIMD already saturates; a second wave
+    // per SIMD has nothing to hide and the per-ray work (draws, sort, marcher) is then done by twice as many waves.
+    // P3D_FLAG_QUAD8 / P3D_FLAG_PAIR16 force one of the two (tests, A/B timing).  No dumps on this path.
+    // Round 5 (profiles/r05_notes.txt): the tolerance-mode quad kernels spill 30 VGPRs instead of 109 (the fold no longer copies its
+    // partial sums) and win at every sample count of a 128^2 view (48+48: 0.42 -> 0.325 ms vs 0.354 for the pair kernel; 96+96: 0.559 vs
+    // 0.618): the tolerance mode takes the quad kernel for every small launch.  The exact quad kernels are compiled for one wave per
+    // SIMD (no spills: 64^2 x (96+96) 0.60 -> 0.50 ms) and stay the choice for <= 8192 rays only.
+    // (Decided on the 32-ray tile count, before the small-launch kernels re-tile.)
+    const bool small = !has_dumps && !(flags & P3D_FLAG_NO_PAIR) && pl.ntiles <= 512;
+    const bool quad = small && !(flags & P3D_FLAG_PAIR16) &&
+                      ((flags & P3D_FLAG_QUAD8) || (long long)N * R <= 8192 || (pl.fast && (pl.nf == 96 || pl.nf == 48)));
+    // the production 96-key kernel keeps no coarse-depth rows (TCG) and runs two waves per SIMD like the others
+    // (for the plain stratified spacing: per-ray limits and disparity spacing keep the LDS-resident 96-key kernel)
+    const bool tcg = pl.nf == 96 && !has_dumps && !small && !(flags & P3D_FLAG_NO_EARLY_OUT) && !has_ray_limits && !disparity;
+
+    // per-wave LDS rows: tc (Sc) + wc/cdf/sorted-fine (max(Sc,Sf)) [+ tf (Sf) on the generic path]
+    // + two bit rows over the merged list (is-coarse / known-masked) + the known-masked bits of the coarse samples
+    pl.lds_rows = Sc + (Sc > Sf ? Sc : Sf) + (pl.nf == 0 ? Sf : 0) + 2 * ((Sc + Sf + 31) >> 5) + ((Sc + 31) >> 5);
+    if (tcg) pl.lds_rows = (Sc > Sf ? Sc : Sf) + 2 * ((Sc + Sf + 31) >> 5);
+    const size_t lds_fixed = (size_t)((pl.fast ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4) * 4;
+    const auto lds = [&](int nwaves) { return lds_fixed + (size_t)nwaves * pl.lds_rows * pl.rays_per_wave * 4; };
+
+    int nw = P3D_RENDER_WAVES;
+    if (small) {
+        pl.slots = quad ? 4 : 2;
+        tile(32 / pl.slots);
+        // P3D_FLAG_WEIGHTS_ONLY: honoured by the tolerance-mode four-slot kernels at 48 / 96 fine samples (what paste_front's occlusion pass runs)
+        const bool wo = quad && pl.fast && (flags & P3D_FLAG_WEIGHTS_ONLY) != 0 && (pl.nf == 48 || pl.nf == 96);
+        pl.kernel = wo ? RenderKernel::SLOTS4_WO : quad ? RenderKernel::SLOTS4 : RenderKernel::SLOTS2;
+        // workgroups per CU the LDS is packed for: two for the four-slot form, the exact one included (whose registers hold it to one
+        // wave per SIMD: p3d_render_slots_occ)
+        const size_t wgs = quad ? 2 : 1;
+        while (nw > 1 && wgs * lds(nw) > P3D_RENDER_LDS_CU) nw >>= 1;
+    } else {
+        pl.slots = 1;
+        pl.kernel = has_dumps ? RenderKernel::DUMP : (flags & P3D_FLAG_NO_EARLY_OUT) ? RenderKernel::PLAIN
+                                                   : tcg ? RenderKernel::EARLY_TCG : RenderKernel::EARLY;
+        // small ray counts: shrink the workgroup so that every CU gets work
+        while (nw > 1 && pl.ntiles / nw < 2 * 256) nw >>= 1;
+        if (nw == P3D_RENDER_WAVES) {
+            // large launch: the workgroup shape (4, 2 or 1 waves, as many workgroups as fit) that puts most waves on a CU, at
+            // most 4 x occ; ties go to the LARGER workgroup.  48+48: 2 x 4 waves; 64+64: 3 x 2 instead of 1 x 4 (measured
+            // 6.85 -> 6.53 ms at 512^2); 96+96: 2 x 4 with the production kernel (TCG), 1 x 4 with the LDS-resident instantiations
+            // (measured there: 2 x 2 waves 13.3 ms, 1 x 5 12.6, 1 x 4 11.2)
+            const int occ = p3d_render_occ(pl.nf, tcg);
+            int best = 0, best_waves = 0;
+            for (int w = P3D_RENDER_WAVES; w >= 1; w >>= 1) {
+                if (lds(w) > P3D_RENDER_LDS_CU) continue;
+                const int fit = (int)(P3D_RENDER_LDS_CU / lds(w)) * w;
+                const int waves = fit > 4 * occ ? 4 * occ / w * w : fit;
+                if (waves > best_waves) { best_waves = waves; best = w; }
+            }
+            if (best == 0) { pl.err = P3D_E_RANGE; return pl; }
+            nw = best;
+        }
+        while (nw > 1 && lds(nw) > P3D_RENDER_LDS_CU) nw >>= 1;
+        // XCD tile order: runs of swz blocks per XCD (measured: 8..64 within 0.5 %, 1..4 and >= 256 about 1-3 % slower) ...
+        pl.swz = 16;
+        // ... or whole 16 x 16-tile super-tiles per XCD run when the tile grid divides into them, and into a multiple of 8 of them:
+        // 384^2 (18 super-tiles on 8 XCDs) loses 2-3 % to the imbalance, every shape with whole super-tiles per XCD is equal or up
+        // to 3 % better (profiles/r05_tile_order_shapes.json)
+        const long long tiles_y = tiled ? pl.tiles_per_img / pl.tiles_x : 0;
+        if (tiled && pl.tiles_x % 16 == 0 && tiles_y % 16 == 0 && 256 % nw == 0 && (pl.ntiles / 256) % 8 == 0) {
+            pl.blocked = 1;
+            pl.swz = 256 / nw;
+        }
+    }
+    if (lds(nw) > P3D_RENDER_LDS_CU) { pl.err = P3D_E_RANGE; return pl; }
+    pl.nwaves = nw;
+    pl.lds_bytes = lds(nw);
+    pl.grid = (unsigned)((pl.ntiles + nw - 1) / nw);
+    pl.block = 64 * nw;
+    const auto steps = [&](int S) { return (long long)((S + pl.slots - 1) / pl.slots); };
+    pl.decode_steps_full = pl.ntiles * (Sf > 0 ? steps(Sc) + steps(Sc + Sf) : steps(Sc));
+    return pl;
+}

@@ -379,20 +379,21 @@ def render(planes_nhwc, rays_o, rays_d, jitter, u, mlp, opts, ray_tile_w=0, dump
     _lib.check(rc, "p3d_render_rng_f32" if rng_seed is not None else "p3d_render_limits_f32")
     if stats is not None:  # synchronises: wave-level decode steps executed (32 samples each) vs the full count
         steps = int(ws[8:16].view(torch.int64).item())
-        tiled = bool(ray_tile_w and R % ray_tile_w == 0 and ray_tile_w % 8 == 0 and (R // ray_tile_w) % 4 == 0)
-        tiles = (R // 32) * N if tiled else -(-R // 32) * N
-        pair = not dumps and not (opts.flags & _lib.P3D_FLAG_NO_PAIR) and tiles <= 512  # the host's choice (p3d_render_f32)
-        quad = pair and not (opts.flags & _lib.P3D_FLAG_PAIR16) and bool((opts.flags & _lib.P3D_FLAG_QUAD8) or N * R <= 8192 or
-                                                                         ((opts.flags & _lib.P3D_FLAG_FAST_COLOR) and ((Sf == 96 and Sc <= 96) or Sf == 48)))
-        kind = ("quad" if quad else "pair") if pair else None
-        slots = {"quad": 4, "pair": 2, None: 1}[kind]  # samples per wave-step, of 32 // slots rays each
-        rpw = 32 // slots
-        tiles = (R // rpw) * N if tiled else -(-R // rpw) * N
-        full = tiles * ((-(-Sc // slots) + -(-(Sc + Sf) // slots)) if Sf > 0 else -(-Sc // slots))
-        stats.update(decode_steps=steps, decode_steps_full=full, small_launch_kernel=pair, small_launch_kind=kind)
+        slots, tiles, full = render_plan_info(N, R, ray_tile_w, opts, dm is not None, rs_t is not None)[:3]
+        kind = {1: None, 2: "pair", 4: "quad"}[slots]  # samples per wave-step, of 32 // slots rays each
+        stats.update(decode_steps=steps, decode_steps_full=full, tiles=tiles, small_launch_kernel=kind is not None, small_launch_kind=kind)
     if weights_only:  # (feat / xyz may have been left unwritten)
         return None, depth, wsum, None
     return (feat, depth, wsum, xyz, d) if dumps else (feat, depth, wsum, xyz)
+
+
+def render_plan_info(N, R, ray_tile_w, opts, has_dumps=False, has_ray_limits=False):
+    """The launch render() makes for these arguments, as the library chose it (include/panic3d_hip.h p3d_render_plan_info):
+    (samples per wave-step: 1 = k_render, 2 / 4 = k_render_slots; tiles; full decode steps; grid; block; dynamic LDS bytes)."""
+    out = (C.c_int64 * 6)()
+    _lib.check(_lib.lib().p3d_render_plan_info(N, R, int(ray_tile_w or 0), C.byref(opts), int(has_dumps), int(has_ray_limits), out, 6),
+               "p3d_render_plan_info")
+    return tuple(out)
 
 
 def _grad_out(t, name, shape):

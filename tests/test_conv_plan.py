@@ -6,15 +6,14 @@ generator's layers: that is the documented dispatch below."""
 import ctypes as C
 import json
 import os
-import shutil
 import subprocess
 
 import pytest
 
 import conv_plan_cases as K
+from host_build import compile_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "panic3d-anime-reconstruction_amd", "csrc")
 X2 = 2  # P3D_CONV_MMA_F16X2
 
 
@@ -92,18 +91,8 @@ DISPATCH = {  # (name, N): main kernel, split-K depth, reduction, last pass, k_a
 }
 
 
-def _host(tmp_path):
-    exe = str(tmp_path / "conv_plan_host")
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    if cxx is None:
-        import panic3d_amd
-        cxx = panic3d_amd._build._hipcc()
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "conv_plan_host.cpp"), "-o", exe])
-    return exe
-
-
 def test_plans_fit_the_workspace_and_follow_the_dispatch_table(tmp_path):
-    exe = _host(tmp_path)
+    exe = compile_host(tmp_path, "conv_plan_host.cpp")
     lines = ["s %d %d %d %d %d %d" % c for c in K.all_cases()]
     calls = [(name, n, I, O, r, up, x_img, y_img, rgb) for n in (1, 4) for name, I, O, r, up, x_img, y_img, rgb in _calls()]
     for name, n, I, O, r, up, x_img, y_img, rgb in calls:

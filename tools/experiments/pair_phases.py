@@ -28,6 +28,6 @@ for scene in ("canonical", "surface"):
                 a.record(); ops.render(nhwc, w.o, w.d, jit, u, w.mlp, opts, ray_tile_w=res); b.record(); torch.cuda.synchronize()
                 ts.append(a.elapsed_time(b))
             row[name + "_ms"] = round(float(np.median(ts)), 4)
-            tiles = R // (16 if st.get("small_launch_kernel") else 32)
+            tiles = st["tiles"]
             row[name + "_steps_per_wave"] = round(st.get("decode_steps", 0) / tiles, 1)
         print(json.dumps(row))
