@@ -52,6 +52,17 @@ int p3d_conv_wgrad_f32(const float* g, int Hg, int Wg, int sg, int ag, int pg, c
                        int ax, int px0, int N, int O, int I, int taps, int Hd, int Wd, float* dw, const float* wk, const float* dscale,
                        float* g_d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward of a ToRGB layer whose channel sums came out of conv1's launch and were finished by p3d_torgb_combine_f32 — the
+ * super-resolution blocks.  The pre-clamp value v is rebuilt from the same shares in the same order as the forward (tile 0, + tile 1,
+ * ..., + bias[r]), so the clamp mask is the forward's own, bit for bit:
+ *   g_y[n][r][y][x]    = g_img[n][r][y][x] * (clamp < 0 || |v| < clamp)
+ *   g_bias[r]          = sum over n, pixels of g_y (or NULL: not computed)
+ *   g_skip[n][r][u][v] = sum over fy, fx < 4 of skip_fir[fy][fx] * g_img[n][r][2u + 2 - fy][2v + 2 - fx] (out of range: 0) — the adjoint
+ *                        of the forward's up-sampled skip image, skip_fir the forward's 4x4 filter (flipped, gain 4); NULL: not computed.
+ * partial [tiles][N][R][H][W], bias [R] or NULL, g_img / g_y [N][R][H][W], g_skip [N][R][H/2][W/2] (H, W even). */
+int p3d_torgb_combine_backward_f32(const float* partial, int tiles, int N, int R, int H, int W, const float* bias, float clamp,
+                                   const float* g_img, float* g_y, float* g_bias, const float* skip_fir, float* g_skip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,7 @@ SYN_GRAD_SIGNATURES = {
     "p3d_mod_backward_f32": (_I, [_P, _P, _I, _I, _L, _P, _P, _P]),
     "p3d_conv_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "p3d_conv_wgrad_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "p3d_torgb_combine_backward_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P]),
 }
 P3D_GRAD_STATS_BYTES = 256  # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
 

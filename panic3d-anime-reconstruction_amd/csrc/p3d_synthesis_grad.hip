@@ -280,8 +280,82 @@ __global__ __launch_bounds__(SG_WG) void k_sg_gd(const float* __restrict__ wk, c
     if (threadIdx.x == 0) g_d[row] = tot / dscale[row];
 }
 
+// ---- backward of a ToRGB layer finished by p3d_torgb_combine_f32 ---------------------------------------------------------------
+// One thread per image value: the pre-clamp value rebuilt exactly as k_torgb_combine builds it (shares added in tile order, then the
+// bias), and g_y = g_img where the clamp let the value through, 0 elsewhere.
+__global__ __launch_bounds__(SG_WG) void k_sg_torgb_combine_bwd(const float* __restrict__ part, int tiles, int64_t slice, int R, int64_t HW,
+                                                                const float* __restrict__ bias, float clamp, const float* __restrict__ g_img,
+                                                                float* __restrict__ g_y) {
+    const int64_t idx = (int64_t)blockIdx.x * SG_WG + threadIdx.x;
+    if (idx >= slice) return;
+    float v = part[idx];
+    for (int t = 1; t < tiles; ++t) v += part[(int64_t)t * slice + idx];
+    if (bias) v = v + bias[(idx / HW) % R];
+    const bool keep = clamp < 0.f || fabsf(v) < clamp;
+    g_y[idx] = keep ? g_img[idx] : 0.f;
+}
+
+// g_bias[r]: one workgroup per channel; lane j sums the pixels j, j + SG_WG, ... of sample 0, then of sample 1, ..., then the lanes
+// are added in the fixed tree of sg_block_sum.
+__global__ __launch_bounds__(SG_WG) void k_sg_torgb_bias_bwd(const float* __restrict__ g_y, int N, int R, int64_t HW, float* __restrict__ g_bias) {
+    __shared__ float red[SG_WG];
+    const int r = blockIdx.x;
+    float sum = 0.f;
+    for (int n = 0; n < N; ++n) {
+        const float* row = g_y + ((int64_t)n * R + r) * HW;
+        for (int64_t p = threadIdx.x; p < HW; p += SG_WG) sum += row[p];
+    }
+    const float tot = sg_block_sum(sum, red);
+    if (threadIdx.x == 0) g_bias[r] = tot;
+}
+
+// The adjoint of the skip connection's up-sampling (k_torgb_combine's four polyphase taps): each skip value collects the image
+// gradient at the 16 positions its taps reached, g_skip[u][v] = sum over fy, fx < 4 of skipf[fy][fx] * g_img[2u + 2 - fy][2v + 2 - fx]
+// (outside the image: 0), in (fy, fx) order.
+__global__ __launch_bounds__(SG_WG) void k_sg_torgb_skip_bwd(const float* __restrict__ g_img, int64_t planes, int H, int W,
+                                                             const float* __restrict__ skipf, float* __restrict__ g_skip) {
+    const int H2 = H >> 1, W2 = W >> 1;
+    const int64_t idx = (int64_t)blockIdx.x * SG_WG + threadIdx.x;
+    if (idx >= planes * H2 * W2) return;
+    const int64_t pl = idx / ((int64_t)H2 * W2);
+    const int q = (int)(idx - pl * H2 * W2), u = q / W2, v = q - u * W2;
+    const float* g = g_img + pl * H * W;
+    float sum = 0.f;
+#pragma unroll
+    for (int fy = 0; fy < 4; ++fy) {
+        const int Y = 2 * u + 2 - fy;
+#pragma unroll
+        for (int fx = 0; fx < 4; ++fx) {
+            const int X = 2 * v + 2 - fx;
+            const bool in = Y >= 0 && Y < H && X >= 0 && X < W;
+            sum = __builtin_fmaf(in ? skipf[fy * 4 + fx] : 0.f, g[in ? (int64_t)Y * W + X : 0], sum);
+        }
+    }
+    g_skip[idx] = sum;
+}
+
 // ---- entry points -----------------------------------------------------------------------------------------------------------
 static const int64_t SG_MAX_GRID = 0x7fffffff;
+
+extern "C" int p3d_torgb_combine_backward_f32(const float* partial, int tiles, int N, int R, int H, int W, const float* bias, float clamp,
+                                              const float* g_img, float* g_y, float* g_bias, const float* skip_fir, float* g_skip,
+                                              void* stream) {
+    if (!partial || !g_img || !g_y || (g_skip && !skip_fir)) return P3D_E_ARG;
+    if (tiles <= 0 || N <= 0 || R <= 0 || H <= 0 || W <= 0) return P3D_E_ARG;
+    if (g_skip && ((H | W) & 1)) return P3D_E_RANGE;
+    const int64_t HW = (int64_t)H * W, slice = (int64_t)N * R * HW;
+    if (slice * tiles >= ((int64_t)1 << 40) || (slice + SG_WG - 1) / SG_WG > SG_MAX_GRID || R > 65535) return P3D_E_RANGE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_sg_torgb_combine_bwd, dim3((unsigned)((slice + SG_WG - 1) / SG_WG)), dim3(SG_WG), 0, st, partial, tiles, slice, R, HW,
+                       bias, clamp, g_img, g_y);
+    if (g_bias) hipLaunchKernelGGL(k_sg_torgb_bias_bwd, dim3((unsigned)R), dim3(SG_WG), 0, st, (const float*)g_y, N, R, HW, g_bias);
+    if (g_skip) {
+        const int64_t E = (int64_t)N * R * (H / 2) * (W / 2);
+        hipLaunchKernelGGL(k_sg_torgb_skip_bwd, dim3((unsigned)((E + SG_WG - 1) / SG_WG)), dim3(SG_WG), 0, st, g_img, (int64_t)N * R, H, W,
+                           skip_fir, g_skip);
+    }
+    return (int)hipGetLastError();
+}
 
 extern "C" int p3d_bias_act_backward_f32(const float* y, const float* g_y, int N, int C, int64_t HW, int act, float alpha, float gain,
                                          float clamp, const float* dscale, float* g_out, float* g_bias_nc, float* g_noise, void* stream) {

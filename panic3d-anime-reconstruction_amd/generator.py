@@ -4,7 +4,8 @@ checkpoint's init kwargs and copy the parameters by name), with the backbone on 
 (stylegan2.py), the volumetric renderer on the fused HIP kernel (renderer.py) and the super-resolution blocks on the same
 modulated-conv kernel.
 
-The super-resolution is inference-only (`image` carries no gradient).  With grad enabled, `image_raw`, `image_depth`,
+The super-resolution is inference-only by default (`image` carries no gradient); set_superresolution_grad() opts in to its HIP
+backward.  With grad enabled, `image_raw`, `image_depth`,
 `image_weights` and `image_xyz` carry gradients through the renderer's HIP backward to the decoder parameters and the planes
 (renderer.py), and from the planes through the synthesis network's HIP backward (stylegan2.SynthesisNetwork) to
 `ws`, the backbone's synthesis parameters, latent injections and conditioning tensors that require grad.  The mapping network
@@ -68,11 +69,20 @@ class SuperresolutionHybrid8XDC(torch.nn.Module):
                                                img_channels=3, is_last=True, conv_clamp=clamp, **block_kwargs)
 
     def forward(self, rgb, x, ws, **block_kwargs):
-        """Inference-only: runs without autograd whatever the caller's grad mode (the returned image carries no gradient)."""
+        """By default inference-only: runs without autograd whatever the caller's grad mode (the returned image carries no gradient).
+        With `record_grad` set (TriPlaneGenerator.set_superresolution_grad) and autograd recording — grad enabled and the feature image,
+        rgb, ws or a parameter of this module requiring grad — the HIP backward is recorded; the image is the no-grad call's bits."""
+        if self._records_grad(rgb, x, ws):
+            return self._forward(rgb, x, ws, grad=True, **block_kwargs)
         with torch.no_grad():
             return self._forward(rgb, x, ws, **block_kwargs)
 
-    def _forward(self, rgb, x, ws, **block_kwargs):
+    def _records_grad(self, rgb, x, ws):
+        if not (self.__dict__.get("record_grad") and torch.is_grad_enabled()):
+            return False
+        return rgb.requires_grad or x.requires_grad or ws.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    def _forward(self, rgb, x, ws, grad=False, **block_kwargs):
         ws_in = ws
         ws = ws[:, -1:, :].expand(-1, 3, -1)  # (`.repeat(1, 3, 1)` of superresolution.py:283 without the copy: the layers only read it)
         if x.shape[-1] != self.input_resolution:
@@ -85,6 +95,13 @@ class SuperresolutionHybrid8XDC(torch.nn.Module):
         if plan is None:
             plan = stylegan2.StylePlan(stylegan2.plan_entries([("block0", self.block0), ("block1", self.block1)], [0, 0]))
             self.__dict__["_style_plan"] = plan
+        if grad:
+            # under autograd: the plan's values carrying the gradient of their float32 restatement; every layer writes its fp32 result,
+            # and each block's ToRGB keeps riding on conv1 (SynthesisBlock grad_rides) — the no-grad call's launches' bits
+            pre = plan.with_grad(ws)
+            x, rgb = self.block0(x.contiguous(), rgb.contiguous(), ws, pre=pre["block0"], grad=True, grad_rides=True, **block_kwargs)
+            x, rgb = self.block1(x, rgb, ws, pre=pre["block1"], grad=True, grad_rides=True, **block_kwargs)
+            return rgb
         pre = plan(ws, memo_of=ws_in)
         # block0.conv1 hands block1.conv0 its operand (an activation image next to the fp32 tensor ToRGB reads): no conversion pass
         ns = stylegan2._next_conv0_styles(self.block1, pre["block1"], self.block0.resolution)
@@ -579,6 +596,9 @@ class TriPlaneGenerator(torch.nn.Module):
         ret["normalize_images"] = normalize_images
         x.update(ret)
         if x.get("paste_params") is not None:  # front-view paste post-process (triplane.py:497-502)
+            if ret["image"].requires_grad:
+                raise NotImplementedError("the front-view paste has no backward: call G.f with paste_params under torch.no_grad(), or turn "
+                                          "the super-resolution's gradient off (set_superresolution_grad(False))")
             from .paste import paste_front
             ret["image_prepaste"] = ret["image"]
             ret["paste"] = paste_front(self, x, ret, **x["paste_params"])
@@ -664,6 +684,15 @@ class TriPlaneGenerator(torch.nn.Module):
                 else:
                     m.mma_f16 = val
         return mode
+
+    def set_superresolution_grad(self, state=True):
+        """Opt-in: let `image` carry gradients.  With the switch on, a call that records autograd runs the super-resolution under
+        autograd with its HIP backward: the image is the no-grad call's bits, and backward reaches the rendered feature
+        image, ws and the super-resolution's parameters.  It keeps ~0.4 GB of fp32 activations per sample alive until backward.  Off (the
+        default): the super-resolution runs under no_grad whatever the caller's mode.  Drops the captured views."""
+        self.__dict__["_view_graphs"] = None
+        self.superresolution.__dict__["record_grad"] = bool(state)
+        return bool(state)
 
     def set_sr_mma_f16(self, state=True):
         """Opt-in: run the super-resolution convolutions on f16 MFMA operands (fp32 accumulate, fp32 activations in HBM).

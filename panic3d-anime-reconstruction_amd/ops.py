@@ -772,9 +772,18 @@ def conv_fuses_torgb(N, I, O, H, W, rgb_channels):
     return r
 
 
-def torgb_combine(partial, bias=None, clamp=None, skip=None, skip_filter=None):
+def torgb_combine(partial, bias=None, clamp=None, skip=None, skip_filter=None, x=None, weight=None, styles=None):
     """The second half of a ToRGB layer whose channel sums came out of conv1's launch (modulated_conv2d(..., rgb_weight=...)):
-    partial [tiles,N,O,H,W] -> `upsample2d(skip, skip_filter) + (sum over tiles + bias)` [N,O,H,W] (p3d_torgb_combine_f32)."""
+    partial [tiles,N,O,H,W] -> `upsample2d(skip, skip_filter) + (sum over tiles + bias)` [N,O,H,W] (p3d_torgb_combine_f32).
+    Under autograd the layer's own inputs say what the shares were made of — x (conv1's fp32 result [N,I,H,W]), weight (the ToRGB
+    parameter [O,I,1,1]) and styles [N,I] — and the HIP backward is recorded (_TorgbCombineFn); the shares themselves carry no
+    gradient."""
+    if x is not None and _wants_grad(x, weight, styles, bias, skip):
+        return _TorgbCombineFn.apply(x, weight, styles, bias, skip, partial, (clamp, skip_filter))
+    return _torgb_combine_impl(partial, bias, clamp, skip, skip_filter)
+
+
+def _torgb_combine_impl(partial, bias=None, clamp=None, skip=None, skip_filter=None):
     partial = _chk(partial, "partial")
     T, N, O, H, W = partial.shape
     if bias is not None:
@@ -793,6 +802,30 @@ def torgb_combine(partial, bias=None, clamp=None, skip=None, skip_filter=None):
                                               _p(skipf), _p(y), _stream())
     _lib.check(rc, "p3d_torgb_combine_f32")
     return y
+
+
+def torgb_combine_backward(partial, g_img, bias=None, clamp=None, skip_filter=None, want_bias=True):
+    """p3d_torgb_combine_backward_f32: (g_y [N,O,H,W] = g_img where the forward's own pre-clamp sums passed the clamp, else 0;
+    g_bias [O] or None; g_skip [N,O,H/2,W/2] — the adjoint of the up-sampled skip image — when skip_filter is given, else None)."""
+    partial, g_img = _chk(partial, "partial"), _chk(g_img, "g_img")
+    T, N, O, H, W = partial.shape
+    if tuple(g_img.shape) != (N, O, H, W):
+        raise RuntimeError("torgb_combine_backward: g_img [N,O,H,W] of partial [tiles,N,O,H,W]")
+    if bias is not None:
+        bias = _chk(bias, "bias")
+    g_y = torch.empty_like(g_img)
+    g_b = torch.empty((O,), dtype=torch.float32, device=g_img.device) if want_bias else None
+    skipf = g_skip = None
+    if skip_filter is not None:
+        skipf = prepared_filter(skip_filter, g_img.device, 4.0, False)  # the forward's filter: the kernel applies its adjoint
+        if tuple(skipf.shape) != (4, 4):
+            raise NotImplementedError("skip_filter must be the 4x4 [1,3,3,1] filter")
+        g_skip = torch.empty((N, O, H // 2, W // 2), dtype=torch.float32, device=g_img.device)
+    with _on(g_img.device):
+        rc = _lib.lib().p3d_torgb_combine_backward_f32(_p(partial), T, N, O, H, W, _p(bias), float(clamp if clamp is not None else -1),
+                                                       _p(g_img), _p(g_y), _p(g_b), _p(skipf), _p(g_skip), _stream())
+    _lib.check(rc, "p3d_torgb_combine_backward_f32")
+    return g_y, g_b, g_skip
 
 
 class WeightOperand(torch.Tensor):
@@ -966,11 +999,22 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, padding=0, resample_fi
     return the result as the ActImage of a following layer with those styles instead of an fp32 tensor.
     rgb_weight [R<=4,O] + rgb_styles [N,O] (plain 3x3 layer with an ActImage input, only where conv_fuses_torgb(...) says so): the
     block's ToRGB layer rides on this launch — the call returns (y, image or None, partial [O/64,N,R,H,W]) and torgb_combine(partial,
-    ...) finishes the ToRGB layer; want_y=False: y is not written (None is returned in its place)."""
+    ...) finishes the ToRGB layer; want_y=False: y is not written (None is returned in its place).  With rgb_weight, x may also be the
+    fp32 tensor: the layer then stages it as its own activation image first (act_to_image with its styles: the hand-over's bits)."""
+    if rgb_weight is not None and isinstance(x, torch.Tensor):
+        if _wants_grad(x, weight, styles, noise, bias, dcoef):
+            # under autograd (the super-resolution's riding ToRGB): y is written for the backward; the shares carry no gradient —
+            # torgb_combine(..., x=y, weight=, styles=) records the ToRGB layer's own backward
+            y, part = _ModConvFn.apply(x, weight, styles, dcoef, bias, noise,
+                                       dict(up=int(up), padding=padding, resample_filter=resample_filter, demodulate=bool(demodulate), act=act,
+                                            gain=gain, clamp=clamp, weight_f16=weight_f16, saturated=saturated,
+                                            ride=(rgb_weight.detach(), rgb_styles.detach())))
+            return y, None, part
+        x = act_to_image(x, styles, saturated=saturated)
     if _wants_grad(x if isinstance(x, torch.Tensor) else None, weight, styles, noise, bias, dcoef):
         # under autograd: the HIP backward (_ModConvFn); the hand-overs below are inference-only
-        if isinstance(x, ActImage) or next_styles is not None or rgb_weight is not None:
-            raise RuntimeError("modulated_conv2d: activation images, next_styles and rgb_weight are inference-only (call under torch.no_grad())")
+        if isinstance(x, ActImage) or next_styles is not None:
+            raise RuntimeError("modulated_conv2d: activation images and next_styles are inference-only (call under torch.no_grad())")
         return _ModConvFn.apply(x, weight, styles, dcoef, bias, noise,
                                 dict(up=int(up), padding=padding, resample_filter=resample_filter, demodulate=bool(demodulate), act=act, gain=gain,
                                      clamp=clamp, weight_f16=weight_f16, saturated=saturated))
@@ -1227,20 +1271,30 @@ class _ModConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, styles, dcoef, bias, noise, kw):
         k = dict(kw)
-        y = _modulated_conv2d_impl(x, weight, styles, noise=noise, up=k["up"], padding=k["padding"], resample_filter=k["resample_filter"],
-                                   demodulate=k["demodulate"], bias=bias, act=k["act"], gain=k["gain"], clamp=k["clamp"],
-                                   weight_f16=k["weight_f16"], dcoef=dcoef, saturated=k["saturated"])
+        ride = k.pop("ride", None)
         if k["demodulate"] and dcoef is None:
             raise RuntimeError("modulated_conv2d under autograd: pass the demodulation coefficients (dcoef)")
+        if ride is not None:  # (the block's ToRGB rides on this launch: x staged as the layer's activation image, y written, the shares out)
+            y, _, part = _modulated_conv2d_impl(act_to_image(x, styles, saturated=k["saturated"]), weight, styles, noise=noise, up=k["up"],
+                                                padding=k["padding"], resample_filter=k["resample_filter"], demodulate=k["demodulate"], bias=bias,
+                                                act=k["act"], gain=k["gain"], clamp=k["clamp"], weight_f16=k["weight_f16"], dcoef=dcoef,
+                                                saturated=k["saturated"], rgb_weight=ride[0], rgb_styles=ride[1], want_y=True)
+            ctx.mark_non_differentiable(part)
+        else:
+            y = _modulated_conv2d_impl(x, weight, styles, noise=noise, up=k["up"], padding=k["padding"], resample_filter=k["resample_filter"],
+                                       demodulate=k["demodulate"], bias=bias, act=k["act"], gain=k["gain"], clamp=k["clamp"],
+                                       weight_f16=k["weight_f16"], dcoef=dcoef, saturated=k["saturated"])
         ctx.kw = k
         ctx.noise_shape = None if noise is None else tuple(noise.shape)
         ctx.save_for_backward(x, weight, styles, dcoef, bias, y)
-        return y
+        return (y, part) if ride is not None else y
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, *_):
         x, weight, styles, dcoef, bias, y = ctx.saved_tensors
         k = ctx.kw
+        if gy is None:
+            gy = torch.zeros_like(y)
         x, styles = x.contiguous(), styles.contiguous()
         N, I, H, W = x.shape
         O, ks = weight.shape[0], weight.shape[-1]
@@ -1271,3 +1325,32 @@ class _ModConvFn(torch.autograd.Function):
             ns = ctx.noise_shape  # one of the forward's three shapes: per sample only as [N,1,H,W] with N > 1
             g_noise = (gn if len(ns) == 4 and ns[0] == N and N > 1 else gn.sum(0)).reshape(ns)
         return (gx, gw, gs, (gd.view_as(dcoef) if gd is not None else None), (gb.sum(0) if bias is not None else None), g_noise, None)
+
+
+class _TorgbCombineFn(torch.autograd.Function):
+    """Backward of a ToRGB layer that rode on its conv1 launch (super-resolution): the clamp mask, the bias gradient and
+    the skip image's adjoint from the forward's own shares (p3d_torgb_combine_backward_f32 — the stand-alone ToRGB kernel would sum the
+    channels in another order, and a mask from other bits is a wrong gradient at the clamp edge); data, style and weight gradients
+    against conv1's fp32 result on the same kernels as _TorgbFn (one tap)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, styles, bias, skip, partial, meta):
+        clamp, skip_filter = meta
+        ctx.meta, ctx.has_skip = meta, skip is not None
+        ctx.save_for_backward(x, weight, styles, bias, partial)
+        return _torgb_combine_impl(partial, bias, clamp, skip, skip_filter)
+
+    @staticmethod
+    def backward(ctx, gimg):
+        x, weight, styles, bias, partial = ctx.saved_tensors
+        clamp, skip_filter = ctx.meta
+        want_skip = ctx.has_skip and ctx.needs_input_grad[4]
+        gz, gb, g_skip = torgb_combine_backward(partial, gimg.contiguous(), bias, clamp, skip_filter if want_skip else None,
+                                                want_bias=bias is not None)
+        x, styles = x.contiguous(), styles.contiguous()
+        N, I, H, W = x.shape
+        O = weight.shape[0]
+        gx = conv_dgrad(gz, weight.detach().reshape(1, O, I).contiguous(), I, H, W, 1, 0)
+        gs = mod_backward(x, styles, gx)
+        dw, _ = conv_wgrad(gz, (1, 0, 0), x, styles, (1, 0, 0), 1, (H, W))
+        return gx, dw.view(weight.shape), gs, gb, g_skip, None, None

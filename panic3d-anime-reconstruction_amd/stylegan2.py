@@ -359,10 +359,11 @@ class ToRGBLayer(_CacheFree):
         return ops.upsample2d_add(skip, skip_filter, y) if skip is not None else y
 
 
-def _torgb_rides(block, x, pre):
+def _torgb_rides(block, x, pre, image_fed=None):
     """(weights [R,O], styles [N,O]) when `block`'s ToRGB layer can ride on its conv1 launch (ops.conv_fuses_torgb: an image-fed
-    plain 3x3 layer on the pipelined kernel, <= 4 image channels — the super-resolution blocks), else None.  x: conv1's input."""
-    if not (CONV_IMG and TORGB_RIDES and isinstance(x, ops.ActImage)):
+    plain 3x3 layer on the pipelined kernel, <= 4 image channels — the super-resolution blocks), else None.  x: conv1's input;
+    image_fed: whether conv1 stages it from an activation image (default: x is an ops.ActImage)."""
+    if not (CONV_IMG and TORGB_RIDES and (isinstance(x, ops.ActImage) if image_fed is None else image_fed)):
         return None
     t = block._modules["torgb"]
     tw = t._parameters["weight"]
@@ -563,14 +564,17 @@ class SynthesisBlock(torch.nn.Module):
         self.num_torgb += 1
 
     def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, update_emas=False, pre=None, x_image=None, next_styles=None,
-                need_x=True, grad=False, **layer_kwargs):
+                need_x=True, grad=False, grad_rides=False, **layer_kwargs):
         """pre: {layer name: (styles, demod coefficients)} from a StylePlan (all affine layers of the network in one GEMM),
         or None: every layer runs its own affine like the reference (networks_stylegan2.py:342,377).
         x_image: x as the ops.ActImage the previous block's conv1 wrote for this block's conv0 (then x itself is not read by conv0);
         next_styles: the styles of the NEXT block's conv0 -> conv1 also writes its result as that layer's image and the block returns
         (x, img, image) instead of (x, img).
         need_x=False: the caller does not read the returned fp32 x (the next block takes the image, or this is the last block) — where
-        the ToRGB layer rides on conv1's launch (_torgb_rides) x is then not written and None is returned in its place."""
+        the ToRGB layer rides on conv1's launch (_torgb_rides) x is then not written and None is returned in its place.
+        grad: record the backward (every layer writes its fp32 result).  grad_rides (the super-resolution): under grad, keep the ToRGB
+        layer riding on conv1 where the no-grad call has it ride — conv1 stages conv0's fp32 result as its activation image itself
+        (the hand-over's bits) and ops.torgb_combine records the riding layer's backward: the no-grad call's image, bit for bit."""
         w_iter = iter(ws.unbind(dim=1))
         pre = pre or {}
         if self.in_channels == 0:
@@ -585,18 +589,22 @@ class SynthesisBlock(torch.nn.Module):
             # conv0 hands conv1 its operand (activation image) when conv1 can stage from one and its styles / demodulation
             # coefficients are known up front (a StylePlan)
             p1 = pre.get("conv1")
-            img_ok = not grad and p1 is not None and p1[1] is not None and _takes_image(self.conv1, self.resolution) and self.conv1.in_channels % 8 == 0
+            img_ok = (not grad or grad_rides) and p1 is not None and p1[1] is not None and _takes_image(self.conv1, self.resolution) \
+                and self.conv1.in_channels % 8 == 0
             x0 = x_image if (x_image is not None and pre.get("conv0") is not None and pre["conv0"][1] is not None) else x.to(torch.float32)
-            x = self.conv0(x0, next(w_iter), pre=pre.get("conv0"), next_styles=p1[0] if img_ok else None, **layer_kwargs)
-            rides = None if grad else _torgb_rides(self, x, pre)
+            # (under grad conv0 writes its fp32 result: its own backward and conv1's read it)
+            x = self.conv0(x0, next(w_iter), pre=pre.get("conv0"), next_styles=p1[0] if (img_ok and not grad) else None, **layer_kwargs)
+            rides = _torgb_rides(self, x, pre, image_fed=img_ok) if (img_ok or not grad) else None
             if rides is not None:  # ToRGB's channel sums from conv1's epilogue, finished by one small launch
                 hand = next_styles if isinstance(x, ops.ActImage) else None
-                x, x_next, part = self.conv1(x, next(w_iter), pre=p1, next_styles=hand, rgb=rides, want_y=need_x or (next_styles is not None and hand is None),
-                                             **layer_kwargs)
+                x, x_next, part = self.conv1(x, next(w_iter), pre=p1, next_styles=hand, rgb=rides,
+                                             want_y=grad or need_x or (next_styles is not None and hand is None), **layer_kwargs)
                 next(w_iter)
                 t = self._modules["torgb"]
-                img = ops.torgb_combine(part, bias=t._parameters["bias"], clamp=t.conv_clamp, skip=None if img is None else img.to(torch.float32),
-                                        skip_filter=self._buffers["resample_filter"])
+                tp = t._parameters
+                rec = dict(x=x, weight=tp["weight"], styles=rides[1]) if grad else {}
+                img = ops.torgb_combine(part, bias=tp["bias"], clamp=t.conv_clamp, skip=None if img is None else img.to(torch.float32),
+                                        skip_filter=self._buffers["resample_filter"], **rec)
                 if next_styles is not None:
                     return x, img, x_next
                 return x, img
