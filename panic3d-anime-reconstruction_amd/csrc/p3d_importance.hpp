@@ -1,0 +1,153 @@
+// The per-ray importance work of k_render that the two halves of a wave share out between them: the sorting-network
+// schedules and the split of the merge pre-pass.  In k_render a lane is (ray j = lane & 31) x (half h = lane >> 5); the
+// halves serve the decode (each owns half of the hidden channels), so anything per ray would run twice with equal results.
+// Here half h owns half of it:
+//
+//   draws       half h makes the inverse-CDF draws [h * Sf/2, (h + 1) * Sf/2);
+//   sort        each half sorts its Sf/2 keys in registers (p3d_sort_network), half 1 on the NEGATED keys, i.e. descending;
+//               one cross-half exchange (p3d_cross_half_exchange: key i of half 0 against key i of half 1) leaves the Sf/2
+//               smallest keys in half 0 and the Sf/2 largest in half 1, each as a sequence that falls and then rises
+//               (half 0 holds its keys negated for that); p3d_valley_merge sorts such a sequence.  Half 1 ends with rank
+//               Sf/2 + i in register i, half 0 with MINUS rank Sf/2 - 1 - i (p3d_half_rank / the sign are applied by the store);
+//   merge       the stable merge of the coarse and the fine column is cut at merged position S/2 (p3d_merge_split finds how many
+//               coarse samples lie in front of the cut); half h walks [h * S/2, ...) and the bit words are OR-ed across halves.
+//
+// The networks only move values (min / max of finite floats; a negation is exact), so the sorted column — and with it every
+// result — is the one any correct sort gives.  Everything here is a template over the key type and its operations, so a host
+// program can run the very schedules on 0-1 inputs, 64 of them per machine word (tests/importance_split_host.cpp).
+#pragma once
+
+#if defined(__HIPCC__)
+#define P3D_IMP_FN __host__ __device__ __forceinline__
+#define P3D_IMP_UNROLL _Pragma("unroll")
+#else
+#define P3D_IMP_FN inline
+#define P3D_IMP_UNROLL
+#endif
+
+// keys on the device: finite floats
+struct P3dFloatKey {
+    P3D_IMP_FN static float mn(float a, float b) { return __builtin_fminf(a, b); }
+    P3D_IMP_FN static float mx(float a, float b) { return __builtin_fmaxf(a, b); }
+    P3D_IMP_FN static float neg(float a) { return -a; }
+};
+
+P3D_IMP_FN constexpr int p3d_pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+// In-register sort of a ray's NR keys: Batcher's odd-even merge sort on N = the next power of two with keys NR..N-1 = +inf:
+// a comparator writes min to the lower and max to the upper index, so one whose upper index is >= NR never changes anything
+// and is simply not emitted (NR = 48: 543 -> 384 comparators, NR = 96: 1471 -> 1056, NR = 24: 191 -> 132).
+// (one pass of it, p3d_sort_merge_pass<NR>(a, pp), merges every pair of neighbouring sorted blocks of pp keys: the unit the host
+// test proves on all sorted 0-1 blocks)
+template <int NR, typename K = P3dFloatKey, typename T>
+P3D_IMP_FN void p3d_sort_merge_pass(T (&a)[NR], int pp) {
+    constexpr int N = p3d_pow2_ceil(NR);
+P3D_IMP_UNROLL
+    for (int k = pp; k >= 1; k >>= 1) {
+P3D_IMP_UNROLL
+        for (int jj = k % pp; jj + k < N; jj += 2 * k) {
+P3D_IMP_UNROLL
+            for (int i = 0; i < k; ++i) {
+                if (i + jj + k < NR && (i + jj) / (2 * pp) == (i + jj + k) / (2 * pp)) {
+                    T x = a[i + jj], y = a[i + jj + k];
+                    a[i + jj] = K::mn(x, y);
+                    a[i + jj + k] = K::mx(x, y);
+                }
+            }
+        }
+    }
+}
+template <int NR, typename K = P3dFloatKey, typename T>
+P3D_IMP_FN void p3d_sort_network(T (&a)[NR]) {
+P3D_IMP_UNROLL
+    for (int pp = 1; pp < p3d_pow2_ceil(NR); pp <<= 1) p3d_sort_merge_pass<NR, K>(a, pp);
+}
+
+// The cross-half exchange on ONE key index, written on the two halves' values: half 0 holds lo = A[i] of its ascending keys,
+// half 1 holds hi_neg = -B[H-1-i] (its keys sorted on their negation).  Half 0 keeps the minimum — negated — and half 1 the
+// maximum.  (-min(a, b) = max(-a, -b): the device gets both results from v_max_f32 with source modifiers.)
+template <typename K = P3dFloatKey, typename T>
+P3D_IMP_FN void p3d_cross_half_exchange(T lo, T hi_neg, T& lo_out_neg, T& hi_out) {
+    lo_out_neg = K::mx(K::neg(lo), hi_neg);
+    hi_out = K::mx(lo, K::neg(hi_neg));
+}
+
+// Ascending sort of H keys that fall and then rise (either part may be empty): the bitonic merge network on N = the next power
+// of two with keys H..N-1 = +inf — the padded sequence still falls and then rises — and, as above, no comparator whose upper
+// index is >= H (H = 24: 52 comparators, H = 48: 128).
+template <int H, typename K = P3dFloatKey, typename T>
+P3D_IMP_FN void p3d_valley_merge(T (&a)[H]) {
+    constexpr int N = p3d_pow2_ceil(H);
+P3D_IMP_UNROLL
+    for (int k = N / 2; k >= 1; k >>= 1) {
+P3D_IMP_UNROLL
+        for (int i = 0; i < H; ++i) {
+            if ((i & k) == 0 && i + k < H) {
+                T x = a[i], y = a[i + k];
+                a[i] = K::mn(x, y);
+                a[i + k] = K::mx(x, y);
+            }
+        }
+    }
+}
+
+// sorted rank (0 .. 2H-1) of the key that register i of half h holds after p3d_valley_merge; half 0 holds it negated
+P3D_IMP_FN constexpr int p3d_half_rank(int H, int h, int i) { return h ? H + i : H - 1 - i; }
+
+// The cut of the stable merge (ties: coarse first) of a sorted coarse column and a sorted fine column at merged position D:
+// the number of coarse samples among the first D merged ones.  rd(true, x) reads coarse rank x, rd(false, k) fine rank k.
+// Coarse x lies at merged position x + #{k : fine(k) < coarse(x)}, which grows with x; it is >= D exactly when D - x <= 0, or
+// D - x <= Sf and fine(D - x - 1) < coarse(x).  The answer is the first x in [max(0, D - Sf), min(D, Sc)] for which that holds
+// (min(D, Sc) if none): a binary search of `steps` rounds (p3d_merge_split_steps), two column reads per round.
+P3D_IMP_FN int p3d_merge_split_steps(int Sc, int Sf) {
+    int n = Sc < Sf ? Sc : Sf, s = 0;  // the interval holds at most min(Sc, Sf) + 1 candidates
+    while (n > 0) { ++s; n >>= 1; }
+    return s;
+}
+template <typename RD>
+P3D_IMP_FN int p3d_merge_split(RD rd, int Sc, int Sf, int D, int steps) {
+    int lo = D - Sf > 0 ? D - Sf : 0, hi = D < Sc ? D : Sc;  // the answer is in [lo, hi]
+    for (int s = 0; s < steps; ++s) {
+        const int mid = (lo + hi) >> 1;  // lo < hi: mid < hi, so coarse `mid` and fine D - mid - 1 exist (clamped for closed intervals)
+        const int cm = mid < Sc - 1 ? mid : Sc - 1, fm = D - mid - 1 < 0 ? 0 : (D - mid - 1 < Sf ? D - mid - 1 : Sf - 1);
+        const bool behind = rd(false, fm) < rd(true, cm);  // coarse `mid` lies at or behind the cut
+        const bool open = lo < hi;
+        hi = (open && behind) ? mid : hi;
+        lo = (open && !behind) ? mid + 1 : lo;
+    }
+    return lo;
+}
+
+// Half h's share of the merge pre-pass: the merged positions [h ? S/2 : 0, h ? S : S/2) of the stable merge, S = Sc + Sf.  For
+// each it decides whether the sample is the head of the coarse list (bit in sw) and whether known(is_coarse, index, depth) says
+// its density needs no decode (bit in kw), and hands every 32-bit word it touched to put(word, kw, sw) — the word that holds the
+// cut gets a part from each half, so put has to OR.  Both halves run S - S/2 steps (the wave's loop is uniform); with S odd
+// half 0's last step is idle.
+template <typename RD, typename KN, typename PUT>
+P3D_IMP_FN void p3d_merge_bits_half(RD rd, KN known, PUT put, int Sc, int Sf, int h) {
+    const int S = Sc + Sf, D = S >> 1, qb = h ? D : 0, qe = h ? S : D;
+    int ci = p3d_merge_split(rd, Sc, Sf, qb, p3d_merge_split_steps(Sc, Sf)), fi = qb - ci;
+    const float inf = __builtin_inff();
+    float ta = rd(true, ci < Sc ? ci : Sc - 1), tb = Sf > 0 ? rd(false, fi < Sf ? fi : Sf - 1) : inf;
+    unsigned kw = 0u, sw = 0u;
+    for (int it = 0; it < S - D; ++it) {
+        const int q = qb + it;
+        const bool mine = q < qe;
+        const bool take_c = (ci < Sc) && (fi >= Sf || ta <= tb);
+        const bool kn = known(take_c, take_c ? ci : fi, take_c ? ta : tb);
+        kw |= (mine && kn) ? (1u << (q & 31)) : 0u;
+        sw |= (mine && take_c) ? (1u << (q & 31)) : 0u;
+        // pop the head of the coarse or of the fine list: ONE read at a selected address and two selects (a store through a
+        // selected pointer parks ta / tb in scratch memory)
+        ci += take_c ? 1 : 0;
+        fi += take_c ? 0 : 1;
+        const int cq = ci < Sc ? ci : Sc - 1, fq = fi < Sf ? fi : (Sf > 0 ? Sf - 1 : 0);
+        const float nv = rd(take_c, take_c ? cq : fq);
+        ta = take_c ? nv : ta;
+        tb = take_c ? tb : nv;
+        if (mine && ((q & 31) == 31 || q == qe - 1)) {
+            put(q >> 5, kw, sw);
+            kw = 0u; sw = 0u;
+        }
+    }
+}

@@ -23,6 +23,8 @@
 
 #include "p3d_decode.hpp"
 #include "p3d_render_plan.hpp"
+#include "p3d_phase_timing.hpp"
+#include "p3d_importance.hpp"
 
 #define P3D_WAVES_PER_WG 4
 // Quad-cooperative gathers (p3d_decode.hpp) in every decode of k_render and k_render_slots (measured with the 76-instruction transpose,
@@ -331,33 +333,7 @@ P3D_DEV float p3d_march_weight(MarchState& st, float t, float sigma, float& tm_o
     return w;
 }
 
-// Batcher odd-even merge sort network on NR register-resident keys; fully unrolled at compile time.  The network is the one for
-// N = the next power of two with keys NR..N-1 = +inf: a comparator writes min to the lower and max to the upper index, so one
-// whose upper index is >= NR never changes anything and is simply not emitted (NR = 48: 543 -> 384 comparators, NR = 96: 1471 ->
-// 1056).
-P3D_DEV constexpr int p3d_pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-template <int NR>
-P3D_DEV void p3d_sort_network(float (&a)[NR]) {
-    constexpr int N = p3d_pow2_ceil(NR);
-#pragma unroll
-    for (int pp = 1; pp < N; pp <<= 1) {
-#pragma unroll
-        for (int k = pp; k >= 1; k >>= 1) {
-#pragma unroll
-            for (int jj = k % pp; jj + k < N; jj += 2 * k) {
-#pragma unroll
-                for (int i = 0; i < k; ++i) {
-                    if (i + jj + k < NR && (i + jj) / (2 * pp) == (i + jj + k) / (2 * pp)) {
-                        float x = a[i + jj], y = a[i + jj + k];
-                        a[i + jj] = __builtin_fminf(x, y);
-                        a[i + jj + k] = __builtin_fmaxf(x, y);
-                    }
-                }
-            }
-        }
-    }
-}
-
+// (the in-register sorting networks: p3d_importance.hpp)
 // insertion sort of rows [0, n) of a per-wave LDS column (generic / rare path)
 template <int RS = 32>  // RS: floats per LDS row (the rays of a wave: 32 in k_render, 32 / SLOTS in k_render_slots)
 P3D_DEV void p3d_lds_insertion_sort(float* A, int n, int j) {
@@ -456,6 +432,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     static_assert(!(DUMP && EARLY), "dumps need every sample decoded");
     static_assert(!TCG || p3d_render_tcg(NF, DUMP, EARLY), "TCG exists only for the production 96-key kernel");
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    P3D_PHASE_START();
     p3d_load_mlp_to_lds(lds, p.w0, p.b0, p.w1, p.b1, !FAST);
     if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
     __syncthreads();
@@ -479,6 +456,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     const int nwaves = blockDim.x >> 6;
     long long tile = bs * nwaves + wave;
     if (tile >= p.ntiles) return;  // no workgroup barrier below this line
+    P3D_PHASE(P3D_PH_WEIGHTS);
     float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * 32;  // per-wave rows, 16-B aligned
 
     const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
@@ -617,6 +595,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             }
         }
     }
+    P3D_PHASE(P3D_PH_STRAT);
     float tmin = __builtin_inff(), tmax = -__builtin_inff();
     if (Sf > 0) {
         // ---- coarse pass, densities only -> ray-marcher weights: renderer.py:179-211
@@ -693,7 +672,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             st.prev_t = t; st.prev_sigma = sigma;
             if constexpr (!DUMP) ndec += skip ? 0 : 1;
         }
-        // ---- sample_importance / sample_pdf: renderer.py:328-387 (per ray; both lanes of a pair compute the same)
+        P3D_PHASE(P3D_PH_COARSE);
+        // ---- sample_importance / sample_pdf: renderer.py:328-387 (per ray; the cdf by both halves, the draws and the sort shared out: p3d_importance.hpp)
         const int Ns = Sc - 3;
         {
             // v[jj] = ws[jj+1] + 1e-5, ws[q] = (max(w[q-1],w[q]) + max(w[q],w[q+1])) * 0.5 + 0.01 ; stored at row jj+1
@@ -716,9 +696,78 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 wcA[(jj + 1) * 32 + j] = (float)acc;  // cdf[jj+1]
             }
         }
+        P3D_PHASE(P3D_PH_CDF);
         const float* uu = p.u + ray * Sf;
         constexpr int DB = 8;  // draws in flight
-        if constexpr (NF > 0) {
+        if constexpr (P3D_NF_EXACT(NF)) {
+            // Half h makes the draws [h * H, (h + 1) * H), sorts them, and after one cross-half exchange and a local merge holds
+            // H of the sorted ranks (p3d_importance.hpp): half 1 rank H + i in register i, half 0 MINUS rank H - 1 - i.
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            constexpr int H = NF / 2;
+            static_assert(H % DB == 0, "whole batches of draws per half");
+            const int d0 = h * H;
+            const uint32_t neg1 = h ? 0x80000000u : 0u, neg0 = h ? 0u : 0x80000000u;  // the sign bit in half 1 / in half 0
+            float tf[H];
+#pragma unroll
+            for (int i = 0; i < H; ++i)  // every load of the half row issued before the first search
+                tf[i] = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, d0 + i) : uu[d0 + i];
+#pragma unroll
+            for (int i0 = 0; i0 < H; i0 += DB) {
+                float ub[DB], vb[DB];
+                int kb[DB];
+#pragma unroll
+                for (int q = 0; q < DB; ++q) ub[q] = tf[i0 + q];
+                if constexpr (TCG) p3d_inverse_cdf<DB, 32>(wcA, tc_raw, Ns, j, ub, vb, kb);
+                else p3d_inverse_cdf<DB, 32>(wcA, tc_lds, Ns, j, ub, vb, kb);
+#pragma unroll
+                for (int q = 0; q < DB; ++q) {
+                    tf[i0 + q] = vb[q];
+                    if constexpr (DUMP) {  // each half writes the entries of its own draws
+                        if (active && p.dumps.depths_fine) p.dumps.depths_fine[ray * Sf + d0 + i0 + q] = vb[q];
+                        if (active && p.dumps.inds) p.dumps.inds[ray * Sf + d0 + i0 + q] = kb[q];
+                    }
+                }
+            }
+            P3D_PHASE(P3D_PH_DRAWS);
+#pragma unroll
+            for (int i = 0; i < H; ++i) tf[i] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tf[i]) ^ neg1);  // half 1 sorts descending
+            p3d_sort_network<H>(tf);
+#pragma unroll
+            for (int i = 0; i < H; i += 2) {
+                // v_permlane32_swap: afterwards lanes 0-31 hold key i of both halves (x: half 0's, y: half 1's), lanes 32-63 key i + 1;
+                // the second swap hands half 0 its (negated) minima and half 1 its maxima back, for both keys
+                u32x2 in = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, tf[i]), __builtin_bit_cast(uint32_t, tf[i + 1]), false, false);
+                const uint32_t in0 = in.x, in1 = in.y;  // (scalars first: a bit cast of a vector ELEMENT reads element 0)
+                float mn_neg, mx;
+                p3d_cross_half_exchange(__builtin_bit_cast(float, in0), __builtin_bit_cast(float, in1), mn_neg, mx);
+                u32x2 out = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, mn_neg), __builtin_bit_cast(uint32_t, mx), false, false);
+                const uint32_t out0 = out.x, out1 = out.y;
+                tf[i] = __builtin_bit_cast(float, out0);
+                tf[i + 1] = __builtin_bit_cast(float, out1);
+            }
+            p3d_valley_merge<H>(tf);
+            // over the cdf rows: every search of BOTH halves is done, and the other half's rows are read below — same wave, so
+            // ordering the wave's own LDS operations is all it takes
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const int row0 = p3d_half_rank(H, h, 0), rstep = h ? 1 : -1;
+            uint64_t crop = 0ull;  // TCG: bit i = the key of register i is cropped
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const float v = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tf[i]) ^ neg0);
+                tfA[(row0 + rstep * i) * 32 + j] = v;
+                if constexpr (TCG) {
+                    const float px = ox + v * dx, pz = oz + v * dz;
+                    crop |= (f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit)) ? (1ull << i) : 0ull;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if constexpr (TCG) {  // register i -> rank: half 1 shifts by H, half 0 mirrors; then each half takes the other's bits
+                static_assert(H >= 32 && H < 64, "the 96 rank bits as 64 + 32");
+                const uint64_t g0 = h ? (crop << H) : (__builtin_bitreverse64(crop) >> (64 - H));
+                fw0 = (uint32_t)g0; fw1 = (uint32_t)(g0 >> 32); fw2 = h ? (uint32_t)(crop >> (64 - H)) : 0u;
+                fw0 |= __shfl_xor(fw0, 32); fw1 |= __shfl_xor(fw1, 32); fw2 |= __shfl_xor(fw2, 32);
+            }
+        } else if constexpr (NF > 0) {  // the padded capacity (NF = 64): both halves do all of it
             float tf[NF];
 #pragma unroll
             for (int i = 0; i < NF; ++i)  // every load of the row issued before the first search
@@ -745,6 +794,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     for (int q = 0; q < DB; ++q) tf[i0 + q] = __builtin_inff();
                 }
             }
+            P3D_PHASE(P3D_PH_DRAWS);
             p3d_sort_network<NF>(tf);
 #pragma unroll
             for (int i = 0; i < NF; ++i)
@@ -777,8 +827,10 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     }
                 }
             }
+            P3D_PHASE(P3D_PH_DRAWS);
             p3d_lds_insertion_sort(tfA, Sf, j);
         }
+        P3D_PHASE(P3D_PH_SORT);
         // unify_samples (renderer.py:289-301) merges two sorted lists; the stratified list is sorted unless rounding
         // reversed two neighbours (practically never) — then sort it too.
         if constexpr (TCG) {
@@ -842,11 +894,12 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             uint32_t slw[6], knw[6];
 #pragma unroll
             for (int w = 0; w < 6; ++w) { slw[w] = 0u; knw[w] = 0u; }
-            for (int i0 = 0; i0 < Sc; i0 += 8) {
+            const int Sch = ((Sc + 15) >> 4) << 3, ib = h * Sch;  // half h searches the coarse ranks [h * Sch, (h + 1) * Sch)
+            for (int i0 = 0; i0 < Sch; i0 += 8) {
                 float tv[8];
                 int pos[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { tv[q] = tc_sorted(i0 + q < Sc ? i0 + q : Sc - 1); pos[q] = 0; }
+                for (int q = 0; q < 8; ++q) { tv[q] = tc_sorted(ib + i0 + q < Sc ? ib + i0 + q : Sc - 1); pos[q] = 0; }
 #pragma unroll
                 for (int step = 64; step >= 1; step >>= 1) {
                     float c[8];
@@ -857,11 +910,10 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    const int i = i0 + q;
-                    if (i >= Sc) break;  // wave-uniform
-                    const uint32_t mwv = (i < 32) ? mw0 : (i < 64 ? mw1 : mw2);  // (i is uniform)
+                    const int i = ib + i0 + q;
+                    const uint32_t mwv = (i < 32) ? mw0 : (i < 64 ? mw1 : mw2);
                     const bool known = is_cropped(tv[q]) || ((mwv >> (i & 31)) & 1u);
-                    const int P = i + pos[q], pw = P >> 5;
+                    const int P = i + pos[q], pw = (i < Sc) ? (P >> 5) : -1;  // (a rank past the end sets no bit)
                     const uint32_t b = 1u << (P & 31);
 #pragma unroll
                     for (int w = 0; w < 6; ++w) {
@@ -870,6 +922,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     }
                 }
             }
+#pragma unroll
+            for (int w = 0; w < 6; ++w) { slw[w] |= __shfl_xor(slw[w], 32); knw[w] |= __shfl_xor(knw[w], 32); }  // the other half's ranks
             // cropped fine samples: fine k sits at the k-th zero of the is-coarse row
             if (__builtin_amdgcn_ballot_w64((fw0 | fw1 | fw2) != 0u) != 0) {
                 int fk = 0;
@@ -894,21 +948,24 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
         } else
         if constexpr (EARLY) {
             // the merge, once: bit q of slA = merged sample q is the head of the coarse list, bit q of knA = its sigma is known
-            uint32_t kw = 0u, sw = 0u;
-            for (int q = 0; q < S; ++q) {
-                const bool take_c = (ci < Sc) && (fi >= Sf || ta <= tb);
-                bool known = is_cropped(take_c ? ta : tb);
-                if (take_c && Sf > 0) known = known || ((mkA[(ci >> 5) * 32 + j] >> (ci & 31)) & 1u);  // Sf == 0: no coarse pass ran
-                kw |= known ? (1u << (q & 31)) : 0u;
-                sw |= take_c ? (1u << (q & 31)) : 0u;
-                advance(take_c);
-                if ((q & 31) == 31 || q == S - 1) {
-                    knA[(q >> 5) * 32 + j] = kw; slA[(q >> 5) * 32 + j] = sw;
-                    kw = 0u; sw = 0u;
-                }
-            }
+            // Half 0 walks the merged positions [0, S/2), half 1 [S/2, S), starting behind the samples that lie in front of the
+            // cut (p3d_importance.hpp).  The word that holds the cut gets bits from both halves, so the rows start at zero and
+            // take their words by LDS OR.
+            for (int w = 0; w < nmw; ++w) { knA[w * 32 + j] = 0u; slA[w * 32 + j] = 0u; }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            p3d_merge_bits_half(
+                [&](bool c, int i) { return (c ? tcA : tfA)[i * 32 + j]; },
+                [&](bool c, int i, float t) {
+                    bool known = is_cropped(t);
+                    if (c && Sf > 0) known = known || ((mkA[(i >> 5) * 32 + j] >> (i & 31)) & 1u);  // Sf == 0: no coarse pass ran
+                    return known;
+                },
+                [&](int w, uint32_t kw, uint32_t sw) { atomicOr(&knA[w * 32 + j], kw); atomicOr(&slA[w * 32 + j], sw); },
+                Sc, Sf, h);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             ci = 0;  // from here on: coarse samples among the first m merged ones (the fine index is m - ci)
         }
+        P3D_PHASE(P3D_PH_MERGE);
         for (int it = 0;; ++it) {
             bool take_c, known = false;  // known: sigma = -1000 without a decode (reached here only behind a sigma > 602)
             float t;
@@ -965,6 +1022,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     if (!done && take_c) tcn = tc_sorted(ci < Sc ? ci : Sc - 1);  // used one step later at the earliest: under the decode
                 }
             }
+            P3D_PHASE(P3D_PH_SELECT);
             const bool have = EARLY ? !done : true;
             const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;
             float sigma = P3D_SIGMA_MASKED;
@@ -981,6 +1039,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 skipped = !live || !have_rgb;  // per lane: a lane whose gathers were suppressed has no colour
                 if (known) sigma = P3D_SIGMA_MASKED;
             }
+            P3D_PHASE(P3D_PH_DECODE);
             if constexpr (DUMP) {
                 if (dump && p.dumps.depths_sorted) p.dumps.depths_sorted[ray * S + m] = t;
                 if (dump && p.dumps.sigma_sorted) p.dumps.sigma_sorted[ray * S + m] = sigma;
@@ -1022,6 +1081,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 first = false;
                 if constexpr (!EARLY) ++m;
             }
+            P3D_PHASE(P3D_PH_MARCH);
         }
     }
     // ---- outputs.  white_back and the [-1,1] rescale are per ray (ray_marcher.py:52-55); the depth clamp is global.
@@ -1056,6 +1116,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
         tmin = __builtin_fminf(tmin, __shfl_xor(tmin, o));
         tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, o));
     }
+    P3D_PHASE(P3D_PH_OUT);
+    P3D_PHASE_FLUSH();
     if (lane == 0) {
         atomicMin(p.gminmax, p3d_f2ord(tmin));
         atomicMax(p.gminmax + 1, p3d_f2ord(tmax));
@@ -1848,6 +1910,19 @@ size_t p3d_render_workspace_bytes(int N, int64_t R, int Sc, int Sf) {
     return p3d_render_plan_workspace_bytes(N);
 }
 
+#ifdef P3D_PHASE_TIMING
+// measurement builds only (tools/phase_timing.py): the section totals of every k_render wave since the last reset
+int p3d_phase_read(unsigned long long* out, int n, int reset) {
+    unsigned long long v[P3D_PH_N];
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(v, HIP_SYMBOL(g_p3d_phase), sizeof(v)) != hipSuccess) return -1;
+    for (int q = 0; q < n && q < P3D_PH_N; ++q) out[q] = v[q];
+    if (reset) {
+        memset(v, 0, sizeof(v));
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_p3d_phase), v, sizeof(v)) != hipSuccess) return -1;
+    }
+    return P3D_PH_N;
+}
+#endif
 int p3d_render_plan_info(int N, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits, int64_t* out, int cap) {
     if (!opts) return P3D_E_ARG;
     const RenderPlan pl = p3d_render_plan(N, R, ray_tile_w, *opts, has_dumps != 0, has_ray_limits != 0);

@@ -1,30 +1,91 @@
-import os, sys, ctypes
-sys.path[:0] = [os.getcwd(), os.path.join(os.getcwd(), "tests")]
-import numpy as np, torch
-import panic3d_amd as P, p3d_testing as T
-from panic3d_amd import ops
-L = P._lib.lib()
-L.p3d_phase_read.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
-dev = torch.device("cuda"); res, Sc, Sf = 512, 48, 48; R = res * res
-ro = T.bench_rendering_kwargs(Sc, Sf)
-for scene in ("canonical", "surface"):
-    planes_np, raw = T.make_bench_scene(scene)
-    nhwc = ops.planes_to_nhwc(torch.from_numpy(planes_np).to(dev))
-    mlp = ops.prescale_mlp(*(torch.from_numpy(x).to(dev) for x in raw), 1 / np.sqrt(32), 1.0, 1 / np.sqrt(64), 1.0)
-    o, d = P.cameras.rays_from_label(P.cameras.camera_label(0.0, 20.0, 1.0, 30.0)[None], res); o, d = o.to(dev), d.to(dev)
-    g = torch.Generator(device=dev).manual_seed(5)
-    jit = torch.rand((1, R, Sc, 1), device=dev, generator=g); u = torch.rand((R, Sf), device=dev, generator=g)
-    for fast in (False, True):
-        for early in (True, False):
-            opts = ops.make_opts(ro, early_out=early, fast_color=fast, **T.BENCH_KW)
-            for _ in range(2): ops.render(nhwc, o, d, jit, u, mlp, opts, ray_tile_w=res)
-            buf = (ctypes.c_ulonglong * 17)(); L.p3d_phase_read(buf, 1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); ops.render(nhwc, o, d, jit, u, mlp, opts, ray_tile_w=res); e1.record(); torch.cuda.synchronize()
-            L.p3d_phase_read(buf, 1)
-            b = list(buf); ms = e0.elapsed_time(e1)
-            tot = b[16]
-            print(f"{scene} fast={fast} early={early}: {ms:.2f} ms | wave lifetime ticks {tot/ max(b[7],1):.0f} per wave ({b[7]} waves) | "
-                  f"coarse: gather {b[0]/tot:.3f} mlp {b[1]/tot:.3f} ({b[4]} steps, {b[0]/max(b[4],1):.0f}+{b[1]/max(b[4],1):.0f} ticks/step) | "
-                  f"final: gather {b[2]/tot:.3f} mlp {b[3]/tot:.3f} ({b[5]} steps, {b[2]/max(b[5],1):.0f}+{b[3]/max(b[5],1):.0f} ticks/step) | other {1-(b[0]+b[1]+b[2]+b[3])/tot:.3f}"
-                  f" || sections: weights->LDS+sync {b[8]/tot:.3f} stratified {b[9]/tot:.3f} coarse loop {b[10]/tot:.3f} cdf {b[11]/tot:.3f} draws+sort {b[12]/tot:.3f} final loop {b[13]/tot:.3f} [merge pre-pass {b[6]/tot:.3f} select/skip {b[14]/tot:.3f} march+composite {b[15]/tot:.3f}]")
+#!/usr/bin/env python3
+"""Per-section clock table of k_render (csrc/p3d_phase_timing.hpp: the -DP3D_PHASE_TIMING measurement build).
+
+    python tools/phase_timing.py --build            # no GPU needed: compiles build/lib_phase.so (48+48 kernels only)
+    python tools/phase_timing.py [-o profiles/X.txt]  # on the GPU: runs the bench view and prints one table per variant
+
+The measurement build is a library of its own; the product library never holds a stamp.  Shares are of the summed wave
+lifetimes; "ticks/wave" are shader cycles per wave WITH the stamps' own cost (~10 %), so compare shares and ratios, not
+milliseconds.
+"""
+import argparse
+import ctypes
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+LIB = os.path.join(ROOT, "build", "lib_phase.so")
+SECTIONS = ["weights->LDS", "stratified", "coarse loop", "cdf", "draws", "sort", "merge pre-pass", "final: select/skip", "final: decode",
+            "final: march+composite", "outputs"]
+N_SLOTS = len(SECTIONS) + 2  # + waves, lifetime
+
+
+def build():
+    """The render unit compiled with the switch (one fine-depth capacity: P3D_ONLY_NF=48), linked with the product's other objects."""
+    import importlib
+    B = importlib.import_module("panic3d_amd")._build
+    objs = [o for o in B._compile_objects() if not os.path.basename(o).startswith("p3d_kernels.hip.")]
+    flags = [f for f in B.HIPCC_FLAGS if f != "-shared"] + ["-DP3D_PHASE_TIMING", "-DP3D_ONLY_NF=48"]
+    obj = os.path.join(ROOT, "build", "p3d_kernels_phase.o")
+    subprocess.check_call([B._hipcc()] + flags + ["-c", os.path.join(B.CSRC, "p3d_kernels.hip"), "-o", obj])
+    subprocess.check_call([B._hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + objs + [obj, "-o", LIB])
+    print("built", LIB)
+
+
+def run(out):
+    os.environ.setdefault("P3D_LIB", LIB)
+    import numpy as np
+    import torch
+    import panic3d_amd as P
+    import p3d_testing as T
+    from panic3d_amd import ops
+    L = P._lib.lib()
+    L.p3d_phase_read.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int, ctypes.c_int]
+    dev = torch.device("cuda")
+    res, Sc, Sf = 512, 48, 48
+    R = res * res
+    ro = T.bench_rendering_kwargs(Sc, Sf)
+    lines = ["# k_render section table, 512^2 rays x (48+48), library " + L.p3d_build_info().decode()]
+    for scene in ("surface", "canonical"):
+        planes_np, raw = T.make_bench_scene(scene)
+        nhwc = ops.planes_to_nhwc(torch.from_numpy(planes_np).to(dev))
+        mlp = ops.prescale_mlp(*(torch.from_numpy(x).to(dev) for x in raw), 1 / np.sqrt(32), 1.0, 1 / np.sqrt(64), 1.0)
+        o, d = P.cameras.rays_from_label(P.cameras.camera_label(0.0, 20.0, 1.0, 30.0)[None], res)
+        o, d = o.to(dev), d.to(dev)
+        g = torch.Generator(device=dev).manual_seed(5)
+        jit = torch.rand((1, R, Sc, 1), device=dev, generator=g)
+        u = torch.rand((R, Sf), device=dev, generator=g)
+        for fast in (False, True):
+            for early in (True, False):
+                opts = ops.make_opts(ro, early_out=early, fast_color=fast, **T.BENCH_KW)
+                for _ in range(2):
+                    ops.render(nhwc, o, d, jit, u, mlp, opts, ray_tile_w=res)
+                buf = (ctypes.c_ulonglong * N_SLOTS)()
+                assert L.p3d_phase_read(buf, N_SLOTS, 1) == N_SLOTS
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ops.render(nhwc, o, d, jit, u, mlp, opts, ray_tile_w=res)
+                e1.record()
+                torch.cuda.synchronize()
+                assert L.p3d_phase_read(buf, N_SLOTS, 1) == N_SLOTS
+                b = list(buf)
+                waves, life = max(b[-2], 1), max(b[-1], 1)
+                lines.append(f"\n{scene} {'tolerance' if fast else 'exact'} early_out={early}: {e0.elapsed_time(e1):.2f} ms with stamps, "
+                             f"{waves} waves, {life / waves:.0f} ticks/wave")
+                for name, v in zip(SECTIONS, b):
+                    lines.append(f"  {name:24s} {v / waves:10.0f} ticks/wave  {v / life:6.3f}")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--build", action="store_true")
+    ap.add_argument("-o", "--out")
+    a = ap.parse_args()
+    build() if a.build else run(a.out)
