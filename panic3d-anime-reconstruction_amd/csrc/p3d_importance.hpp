@@ -13,8 +13,9 @@
 //               coarse samples lie in front of the cut); half h walks [h * S/2, ...) and the bit words are OR-ed across halves.
 //
 // The networks only move values (min / max of finite floats; a negation is exact), so the sorted column — and with it every
-// result — is the one any correct sort gives.  Everything here is a template over the key type and its operations, so a host
-// program can run the very schedules on 0-1 inputs, 64 of them per machine word (tests/importance_split_host.cpp).
+// result — is the one any correct sort gives.  The schedules are templates over the key type and its operations, so a host
+// program can run the very schedules on 0-1 inputs, 64 of them per machine word (tests/importance_split_host.cpp); the block at
+// the end (under __HIPCC__) holds the pieces that need the lanes of a wave and is device only.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -151,3 +152,119 @@ P3D_IMP_FN void p3d_merge_bits_half(RD rd, KN known, PUT put, int Sc, int Sf, in
         }
     }
 }
+
+#if defined(__HIPCC__)
+// ---- device only: the pieces of the split that need the lanes of a wave
+// The sort of the split (see the top of this file): in, half h's H = Sf/2 draws; out, half 1 holds rank H + i in register i,
+// half 0 MINUS rank H - 1 - i (p3d_half_rank).
+template <int H>
+__device__ __forceinline__ void p3d_sort_halves(float (&tf)[H], int h) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const uint32_t neg1 = h ? 0x80000000u : 0u;  // the sign bit in half 1
+P3D_IMP_UNROLL
+    for (int i = 0; i < H; ++i) tf[i] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tf[i]) ^ neg1);  // half 1 sorts descending
+    p3d_sort_network<H>(tf);
+P3D_IMP_UNROLL
+    for (int i = 0; i < H; i += 2) {
+        // v_permlane32_swap: afterwards lanes 0-31 hold key i of both halves (x: half 0's, y: half 1's), lanes 32-63 key i + 1;
+        // the second swap hands half 0 its (negated) minima and half 1 its maxima back, for both keys
+        u32x2 in = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, tf[i]), __builtin_bit_cast(uint32_t, tf[i + 1]), false, false);
+        const uint32_t in0 = in.x, in1 = in.y;  // (scalars first: a bit cast of a vector ELEMENT reads element 0)
+        float mn_neg, mx;
+        p3d_cross_half_exchange(__builtin_bit_cast(float, in0), __builtin_bit_cast(float, in1), mn_neg, mx);
+        u32x2 out = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, mn_neg), __builtin_bit_cast(uint32_t, mx), false, false);
+        const uint32_t out0 = out.x, out1 = out.y;
+        tf[i] = __builtin_bit_cast(float, out0);
+        tf[i + 1] = __builtin_bit_cast(float, out1);
+    }
+    p3d_valley_merge<H>(tf);
+}
+
+// k_render's TCG instantiations keep no coarse-depth column: raw(i) recomputes coarse depth i in DRAW order.  This is the coarse
+// depth of sorted RANK i (what the stable sort of renderer.py:289-301 puts there): the draw-order value itself unless the wave
+// saw a reversed pair (wave_unsorted) — then the neighbour that rounding swapped in, or (wave_bad: jitter outside [0, 1), never from
+// torch.rand_like) the rank-i element of the row by counting, O(Sc^2) reads per access: slow, exact, reached by no renderer.py call.
+template <typename RAW>
+__device__ __forceinline__ float p3d_coarse_rank(RAW raw, int i, int Sc, bool wave_unsorted, bool wave_bad) {
+    float a = raw(i);
+    if (wave_unsorted) {  // wave-uniform
+        if (!wave_bad) {
+            const float lo = i > 0 ? raw(i - 1) : -__builtin_inff(), hi = i < Sc - 1 ? raw(i + 1) : __builtin_inff();
+            a = lo > a ? lo : (a > hi ? hi : a);
+        } else {
+            for (int c = 0; c < Sc; ++c) {
+                const float tv = raw(c);
+                int r = 0;
+                for (int x = 0; x < Sc; ++x) {
+                    const float tx = raw(x);
+                    r += (tx < tv || (tx == tv && x < c)) ? 1 : 0;
+                }
+                a = (r == i) ? tv : a;
+            }
+        }
+    }
+    return a;
+}
+
+// The merge pre-pass without a coarse column (TCG; p3d_merge_bits_half is its counterpart with one): coarse rank i lands at merged
+// position i + #{fine < t_i} (ties: coarse first), found by a search in the sorted fine column fine(k), eight ranks in flight; half
+// h searches the coarse ranks [h * Sch, (h + 1) * Sch).  The two bit rows are built in registers (six words each: Sc + Sf <= 192), OR-ed
+// across the halves and handed to put(word, kw, sw) once.  known(i, t): coarse rank i at depth t needs no decode; fw0-2: sorted fine
+// sample k is cropped — fine k sits at the k-th zero of the is-coarse row.
+template <typename TCS, typename FINE, typename KN, typename PUT>
+__device__ __forceinline__ void p3d_merge_bits_ranks(TCS tc_sorted, FINE fine, KN known, PUT put, uint32_t fw0, uint32_t fw1, uint32_t fw2,
+                                                     int Sc, int Sf, int h) {
+    const int S = Sc + Sf, nmw = (S + 31) >> 5;
+    uint32_t slw[6], knw[6];
+P3D_IMP_UNROLL
+    for (int w = 0; w < 6; ++w) { slw[w] = 0u; knw[w] = 0u; }
+    const int Sch = ((Sc + 15) >> 4) << 3, ib = h * Sch;
+    for (int i0 = 0; i0 < Sch; i0 += 8) {
+        float tv[8];
+        int pos[8];
+P3D_IMP_UNROLL
+        for (int q = 0; q < 8; ++q) { tv[q] = tc_sorted(ib + i0 + q < Sc ? ib + i0 + q : Sc - 1); pos[q] = 0; }
+P3D_IMP_UNROLL
+        for (int step = 64; step >= 1; step >>= 1) {
+            float c[8];
+P3D_IMP_UNROLL
+            for (int q = 0; q < 8; ++q) c[q] = fine((pos[q] + step <= Sf) ? pos[q] + step - 1 : 0);
+P3D_IMP_UNROLL
+            for (int q = 0; q < 8; ++q) pos[q] = ((pos[q] + step <= Sf) && (c[q] < tv[q])) ? pos[q] + step : pos[q];
+        }
+P3D_IMP_UNROLL
+        for (int q = 0; q < 8; ++q) {
+            const int i = ib + i0 + q;
+            const bool kn = known(i, tv[q]);
+            const int P = i + pos[q], pw = (i < Sc) ? (P >> 5) : -1;  // (a rank past the end sets no bit)
+            const uint32_t b = 1u << (P & 31);
+P3D_IMP_UNROLL
+            for (int w = 0; w < 6; ++w) {
+                slw[w] |= (pw == w) ? b : 0u;
+                knw[w] |= (pw == w && kn) ? b : 0u;
+            }
+        }
+    }
+P3D_IMP_UNROLL
+    for (int w = 0; w < 6; ++w) { slw[w] |= __shfl_xor(slw[w], 32); knw[w] |= __shfl_xor(knw[w], 32); }  // the other half's ranks
+    if (__builtin_amdgcn_ballot_w64((fw0 | fw1 | fw2) != 0u) != 0) {
+        int fk = 0;
+P3D_IMP_UNROLL
+        for (int w = 0; w < 6; ++w) {
+            if (w * 32 < S) {  // wave-uniform
+                uint32_t kk = 0u;
+                for (int b = 0; b < 32; ++b) {
+                    const bool isf = !((slw[w] >> b) & 1u) && (w * 32 + b < S);
+                    const uint32_t fwv = (fk < 32) ? fw0 : (fk < 64 ? fw1 : fw2);
+                    kk |= (isf && ((fwv >> (fk & 31)) & 1u)) ? (1u << b) : 0u;
+                    fk += isf ? 1 : 0;
+                }
+                knw[w] |= kk;
+            }
+        }
+    }
+P3D_IMP_UNROLL
+    for (int w = 0; w < 6; ++w)
+        if (w < nmw) put(w, knw[w], slw[w]);
+}
+#endif

@@ -11,7 +11,8 @@
 //   k_render_finish    the one cross-ray dependency: depth clamp to the global [min t, max t] (ray_marcher.py:49-50).
 //   k_sigma2density    get_eg3d_volume's activation + crop / cull masks in one pass.
 //   k_stratified / k_composite / k_importance / k_unify_perm   operator-level stand-alone stages (one thread per ray).
-//
+// The per-ray phases are defined once in p3d_ray_phases.hpp (what the two lane halves share out: p3d_importance.hpp); the render
+// kernels here are the order in which a wave goes through them.
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see panic3d-anime-reconstruction_amd/_build.py).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -21,10 +22,9 @@
 #include <atomic>
 #include <type_traits>
 
-#include "p3d_decode.hpp"
+#include "p3d_ray_phases.hpp"
 #include "p3d_render_plan.hpp"
 #include "p3d_phase_timing.hpp"
-#include "p3d_importance.hpp"
 
 #define P3D_WAVES_PER_WG 4
 // Quad-cooperative gathers (p3d_decode.hpp) in every decode of k_render and k_render_slots (measured with the 76-instruction transpose,
@@ -271,127 +271,6 @@ __global__ __launch_bounds__(P3D_WG, 2) void k_decode_features(DecodeFeatParams 
 // =====================================================================================================================
 // fused ImportanceRenderer.forward
 // =====================================================================================================================
-struct RenderParams {
-    const float* planes;  // [N][3][H][W][32]
-    const float *rays_o, *rays_d;  // [N][R][3]
-    const float* jitter;  // [N][R][Sc]
-    const float* u;       // [N*R][Sf]
-    const float *w0, *b0, *w1, *b1;
-    float *out_feat, *out_depth, *out_wsum, *out_xyz;
-    uint32_t* gminmax;  // [0..1] order-mapped min / max of all depths, [2..3] decode-step count, [4 + 2n ..] per-view min / max
-    int per_view_clamp;  // P3D_FLAG_PER_VIEW_CLAMP: the N views are N calls of the reference -> one clamp range each
-    p3d_dumps dumps;
-    long long R;
-    long long tiles_per_img, ntiles;
-    int tile_w;       // >0: 8x4 screen tiles over a tile_w-wide image
-    int tiles_x;      // tile_w / 8
-    int H, W;
-    int Sc, Sf;
-    float ray_start, ray_end, depth_delta;
-    const float *ray_start_arr, *ray_end_arr;  // per-ray limits [N][R] ('auto', renderer.py:165-171) or null
-    int disparity;                             // P3D_FLAG_DISPARITY
-    int white_back;
-    int lds_rows;     // rows (of 32 floats) of per-wave LDS
-    int rng;          // p3d_render_rng_f32: the two draws come from the counter-based generator of include/p3d_numerics.h
-    uint32_t seed_lo, seed_hi;
-    int swz;          // XCD swizzle run length (blocks)
-    int blocked;      // k_render: tiles ordered by 16 x 16-tile super-tiles, one per XCD run (see the kernel)
-    P3dDecodeCfg cfg;
-};
-
-// per-ray running state of MipRayMarcher2 (ray_marcher.py:25-57)
-struct MarchState {
-    double Td;
-    float W, D;
-    float prev_t, prev_sigma;
-};
-
-// The counter-based generator of p3d_render_rng_f32 (include/p3d_numerics.h "device draws"): stream 0 = the jitter of
-// sample_stratified (renderer.py:324), stream 1 = the u of sample_pdf (:371); a pure function of (seed, stream, ray, index).
-P3D_DEV uint32_t p3d_fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-P3D_DEV float p3d_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, size_t ray, int idx) {
-    uint32_t h = p3d_fmix32(seed_lo ^ ((uint32_t)ray * 0x9E3779B1u));
-    h = p3d_fmix32(h ^ seed_hi ^ ((uint32_t)((unsigned long long)ray >> 32) * 0x7FEB352Du) ^ (((uint32_t)idx * 2u + stream) * 0x846CA68Bu));
-    return (float)(h >> 8) * 0x1p-24f;  // 24 random bits in [0, 1): exact in binary32
-}
-
-// weight of interval (prev, cur); advances the transmittance.  ray_marcher.py:26-42
-P3D_DEV float p3d_march_weight(MarchState& st, float t, float sigma, float& tm_out) {
-    float dl = t - st.prev_t;
-    float sm = (st.prev_sigma + sigma) * 0.5f;
-    float tm = (st.prev_t + t) * 0.5f;
-    float rho = p3d_softplus(sm - 1.0f);
-    float dd = rho * dl;
-    float alpha = 1.0f - p3d_exp(-dd);
-    float T = (float)st.Td;
-    float w = alpha * T;
-    st.Td = st.Td * (double)((1.0f - alpha) + 1e-10f);
-    tm_out = tm;
-    return w;
-}
-
-// (the in-register sorting networks: p3d_importance.hpp)
-// insertion sort of rows [0, n) of a per-wave LDS column (generic / rare path)
-template <int RS = 32>  // RS: floats per LDS row (the rays of a wave: 32 in k_render, 32 / SLOTS in k_render_slots)
-P3D_DEV void p3d_lds_insertion_sort(float* A, int n, int j) {
-    for (int i = 1; i < n; ++i) {
-        float key = A[i * RS + j];
-        int q = i - 1;
-        while (q >= 0) {
-            float v = A[q * RS + j];
-            if (!(v > key)) break;
-            A[(q + 1) * RS + j] = v;
-            --q;
-        }
-        A[(q + 1) * RS + j] = key;
-    }
-}
-
-// B independent inverse-CDF draws: renderer.py:371-386.  cdf rows [0, Ns] of the LDS column j (RS floats per row); the coarse
-// depths, rows [0, Sc), behind a functor tc(index): an LDS column, or in k_render's TCG instantiations recomputed from the jitter
-// tensor.  The B LDS reads of every search step are in flight together (one draw is a chain of 8 dependent LDS round trips; 48 of
-// them back to back were ~9 % of k_render).
-template <int B, int RS, typename TCF>
-P3D_DEV void p3d_inverse_cdf(const float* cdfA, TCF tc, int Ns, int j, const float (&ui)[B], float (&out)[B], int (&k_out)[B]) {
-    // k = #{q in 0..Ns : cdf[q] <= u}  (searchsorted right=True): branchless binary search on the non-decreasing cdf
-    const int n = Ns + 1;
-    int pos[B];
-#pragma unroll
-    for (int q = 0; q < B; ++q) pos[q] = 0;
-#pragma unroll
-    for (int step = 128; step >= 1; step >>= 1) {
-        if (step <= n) {  // wave-uniform
-            float c[B];
-#pragma unroll
-            for (int q = 0; q < B; ++q) c[q] = cdfA[((pos[q] + step <= n) ? pos[q] + step - 1 : 0) * RS + j];
-#pragma unroll
-            for (int q = 0; q < B; ++q) pos[q] = ((pos[q] + step <= n) && (c[q] <= ui[q])) ? pos[q] + step : pos[q];
-        }
-    }
-    float cb[B], ca[B], t0[B], t1[B], t2[B], t3[B];
-#pragma unroll
-    for (int q = 0; q < B; ++q) {
-        const int k = pos[q], below = k - 1 > 0 ? k - 1 : 0, above = k < Ns ? k : Ns;
-        k_out[q] = k;
-        cb[q] = cdfA[below * RS + j]; ca[q] = cdfA[above * RS + j];
-        t0[q] = tc(below); t1[q] = tc(below + 1);
-        t2[q] = tc(above); t3[q] = tc(above + 1);
-    }
-#pragma unroll
-    for (int q = 0; q < B; ++q) {
-        float den = ca[q] - cb[q];
-        if (den < 1e-5f) den = 1.0f;
-        const float bb = 0.5f * (t0[q] + t1[q]), ba = 0.5f * (t2[q] + t3[q]);
-        out[q] = bb + ((ui[q] - cb[q]) / den) * (ba - bb);
-        // the result exists HERE: without this the optimiser sinks the lerp (and keeps its six LDS operands alive) down to the
-        // first use — the sorting network behind the last batch: 6 x Sf live values, 82-169 spilled VGPRs in the NF = 48 / 96 kernels
-        asm volatile("" : "+v"(out[q]));
-    }
-}
-
 // NF: register capacity for the fine depths (sorted by a network); NF == 0: generic path, fine depths sorted in LDS.
 //   NF = 48 / 96: Sf == NF exactly (the trainer's 48+48 and the eval-faithful 96+96 of eg3dc_v0.py:30-31): no padding keys, no
 //   `i < Sf` predicates (64 uniform predicates held in SGPR pairs were the 102-107 SGPR spills of round 2's NF = 64 kernels);
@@ -422,10 +301,22 @@ P3D_DEV void p3d_inverse_cdf(const float* cdfA, TCF tc, int Ns, int j, const flo
 // current decode.  Rows per wave: max(Sc, Sf) + 12 bit rows = 108 -> 13.8 KB -> 8 waves per CU, two per SIMD, also with the
 // tolerance-mode LDS image; the known-masked bits of the coarse samples live in three registers.  With jitter in [0, 1), as
 // torch.rand_like produces it, the stratified depths can be out of order only between NEIGHBOURS (rounding), which the sorted
-// accessor resolves with two more reads; any other disorder takes an exact O(Sc^2) selection (tc_sorted below).
+// accessor resolves with two more reads; any other disorder takes an exact O(Sc^2) selection (p3d_coarse_rank, p3d_importance.hpp).
+// The final pass merges on the fly (ties: coarse first = stable), decodes and composites [rgb | xyz]: renderer.py:243-259.
+// Every lane walks ITS OWN merged list.  With the early-outs on, a lane first consumes — without a decode — every sample
+// whose sigma = -1000 is already known (cropped by position, or a coarse sample the coarse pass really decoded and found
+// masked) while the previous sample's sigma is <= 602: the interval's softplus argument is then <= -200, rho = alpha = w = 0
+// and Td * (double)(1.0f + 1e-10f) = Td, i.e. the marcher update is exactly the identity (include/p3d_numerics.h); only
+// prev_t / prev_sigma move.  A dead ray (Td < 1e-60: every later weight is exactly 0) drops all its remaining samples.
+// The merge itself runs ONCE, ahead of the walk, as a uniform loop that leaves two bit rows per lane in LDS (merged sample q
+// is coarse / is known); the walk then jumps over a whole run of known samples with a count-trailing-ones — consuming them
+// one at a time was a chain of two LDS round trips per sample and a quarter of the kernel (profiles/history/r02_notes.txt).
+// What is left — the samples that can matter — is decoded one per wave-step until every lane has finished, so a tile of
+// rays that miss the subject runs ~Sf/2 steps instead of Sc + Sf.  A consumed sample's colour is fetched after all if one
+// of its interval weights turns out non-zero (sigma of a neighbour >= ~794): results are bit-identical by construction.
 #define P3D_NF_EXACT(NF) ((NF) == 48 || (NF) == 96)
 // TCG is a template parameter of its own (default: on wherever it can be): the plan turns it OFF for the launches whose coarse
-// depths are not the plain stratified spacing — per-ray limits (ray_start = 'auto') and disparity spacing — which depth_of() below
+// depths are not the plain stratified spacing — per-ray limits (ray_start = 'auto') and disparity spacing — which p3d_stratified_fixed()
 // does not know (with TCG derived from (NF, DUMP, EARLY) alone those launches silently rendered the fixed spacing).
 template <int NF, bool DUMP, bool FAST, bool EARLY, bool TCG = p3d_render_tcg(NF, DUMP, EARLY)>
 __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) void k_render(RenderParams p) {
@@ -437,154 +328,53 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-    // XCD-aware block swizzle: hardware places block b on XCD b % 8; give each XCD a contiguous range of tiles so that
-    // the plane texels its rays touch stay in that XCD's L2.
-    // Each XCD gets runs of `swz` consecutive blocks, the runs interleaved round-robin over the 8 XCDs: contiguous enough for
-    // L2 reuse, fine enough that the XCDs finish together although the early-outs make the work per tile uneven.
-    long long nblk = gridDim.x, b = blockIdx.x;
-    const long long swz = p.swz;
-    long long full = (nblk / (8 * swz)) * (8 * swz);
-    long long bs = b;
-    if (b < full) {
-        long long slot = b >> 3, x = b & 7;  // slot-th block of XCD x
-        // p.blocked (round 5): a run is one 16 x 16-tile SUPER-TILE (below); XCD x takes element (x + g) % 8 of group g of eight runs,
-        // so that over its runs it visits every column of super-tiles (the subject sits in the middle columns: a fixed column per
-        // XCD would leave the XCDs of the outer columns idle early)
-        const long long g = slot / swz, xr = p.blocked ? ((x + g) & 7) : x;
-        bs = g * (8 * swz) + xr * swz + (slot % swz);
-    }
-    const int nwaves = blockDim.x >> 6;
-    long long tile = bs * nwaves + wave;
+    // ---- tile -> ray, wave set-up
+    const long long tile = p3d_render_wave_tile(p, wave);
     if (tile >= p.ntiles) return;  // no workgroup barrier below this line
     P3D_PHASE(P3D_PH_WEIGHTS);
     float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * 32;  // per-wave rows, 16-B aligned
-
     const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
-    long long n = tile / p.tiles_per_img, tl = tile - n * p.tiles_per_img;
-    long long r;
-    if (p.tile_w > 0) {
-        long long ty = tl / p.tiles_x, tx = tl - ty * p.tiles_x;
-        if (p.blocked) {
-            // Blocked tile order (round 5): consecutive tiles fill a SUPER-TILE of 16 x 16 tiles (128 x 64 pixels)
-            // before the next one starts, and the XCD swizzle above hands an XCD whole super-tiles — so the ~256 waves resident on an
-            // XCD march through a compact screen block whose footprint in the three planes (x-extent 1/4, y-extent 1/8 of the image:
-            // ~0.3 + 2.1 + 1.0 MB) fits that XCD's 4 MB L2.  Row-major order gave an XCD four full-width tile rows: the whole xz plane
-            // (8.4 MB) streamed through every L2 (measured round 4: the 25 MB of planes fetched ~5 x per XCD).  A pure permutation of
-            // which wave renders which tile: results are bit-identical.  The host sets it when the tile grid divides into super-tiles.
-            const long long st = tl >> 8;
-            const int q = (int)(tl & 255), SX = p.tiles_x >> 4;
-            tx = (st % SX) * 16 + (q & 15);
-            ty = (st / SX) * 16 + (q >> 4);
-        }
-        // 8x4 pixel tile in Morton-like lane order: every lane quad is a 2x2 pixel block, so the quad's four gathers of a
-        // tap fall into 1-2 cache lines (the L1 coalesces within a quad; rocprof: TCP accesses/instr 48 -> see DESIGN.md)
-        const int lx = (j & 1) | ((j >> 1) & 6), ly = ((j >> 1) & 1) | ((j >> 3) & 2);
-        r = (ty * 4 + ly) * p.tile_w + tx * 8 + lx;
-    } else {
-        r = tl * 32 + j;
-    }
-    const bool active = r < p.R;
-    const long long rc = active ? r : p.R - 1;
-    const size_t ray = (size_t)n * p.R + rc;
-
-    P3dPlaneGeom g;
-    g.halfW = 0.5f * (float)p.W; g.halfH = 0.5f * (float)p.H; g.fW = (float)p.W; g.fH = (float)p.H; g.W = p.W;
-    g.plane_bytes = (uint32_t)p.H * (uint32_t)p.W * 128u;
-    unsigned nlo = __builtin_amdgcn_readfirstlane((unsigned)n);
-    const float* pbase = p.planes + ((p.cfg.flags & P3D_FLAG_SHARED_PLANES) ? (size_t)0 : (size_t)nlo * 3 * (g.plane_bytes / 4));
-    auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)pbase, 0, 3 * g.plane_bytes, 0x00020000);
-    const P3dDecodeCfg cfg = p.cfg;
+    const P3dRayCtx cx = p3d_ray_setup(p, p3d_render_tile_ray(p, tile, j), Sc, Sf);
+    const bool active = cx.active;
+    const size_t ray = cx.ray;
+    const float ox = cx.ox, oy = cx.oy, oz = cx.oz, dx = cx.dx, dy = cx.dy, dz = cx.dz;
     constexpr bool early = EARLY;
-    const bool f_crop = (cfg.flags & P3D_FLAG_CROP) != 0;
     int ndec = 0;  // decode steps this wave executed (statistics)
-
-    const float ox = p.rays_o[ray * 3], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
-    const float dx = p.rays_d[ray * 3], dy = p.rays_d[ray * 3 + 1], dz = p.rays_d[ray * 3 + 2];
 
     // LDS rows of this wave: row(i)[j]
     float* tcA = wl;             // [Sc]            coarse depths (TCG: no such rows)
     float* wcA = TCG ? wl : tcA + Sc * 32;  // [max(Sc,Sf)]    coarse weights -> pdf/cdf (row 0 = cdf[0]) -> (NF path) sorted fine depths
     float* tfA = (NF > 0) ? wcA : wcA + Sc * 32;  // [Sf] sorted fine depths
-    auto tc_lds = [&](int i) { return tcA[i * 32 + j]; };
     uint32_t* mkA = (uint32_t*)(wl + (size_t)(p.lds_rows - ((Sc + 31) >> 5)) * 32);  // [ceil(Sc/32)] known-masked bits of the coarse samples
     const int nmw = (S + 31) >> 5;                         // words of a bit row over the merged list
     uint32_t* knA = TCG ? (uint32_t*)(wl + (size_t)(Sc > Sf ? Sc : Sf) * 32) : mkA - (size_t)2 * nmw * 32;  // [ceil(S/32)] merged sample q: sigma = -1000 known without a decode
     uint32_t* slA = knA + (size_t)nmw * 32;                // [ceil(S/32)] merged sample q comes from the coarse list
-    // ---- the stratified depth of coarse sample i from its jitter value (renderer.py:324-326): the plain branch of the loop
-    // below as a function (the host launches a TCG instantiation only for it: fixed ray_start / ray_end, no disparity spacing)
-    const float sd_step = (p.ray_end - p.ray_start) / (float)(Sc - 1);
-    auto depth_of = [&](int i, float jv) -> float {
-        const float lin = (i < Sc / 2) ? p3d_fma(sd_step, (float)i, p.ray_start) : p3d_fma(-sd_step, (float)(Sc - 1 - i), p.ray_end);
-        return lin + jv * p.depth_delta;
-    };
-    const float* jitp = p.jitter + ray * Sc;  // (not dereferenced with the in-kernel generator)
-    auto jit_at = [&](int i) -> float { return p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 0u, ray, i) : jitp[i]; };
-    auto tc_raw = [&](int i) -> float { return depth_of(i, jit_at(i)); };  // coarse depth i in DRAW order (bins of the pdf)
+    // TCG knows the fixed spacing only (the host launches a TCG instantiation only for it: fixed ray_start / ray_end, no disparity)
+    const P3dSpacing sp = TCG ? p3d_spacing_fixed(p.ray_start, p.ray_end, p.depth_delta, Sc) : p3d_spacing_of(p, ray, Sc);
+    auto tc_raw = [&](int i) -> float { return p3d_stratified_fixed(i, Sc, cx.jitter(i), sp); };  // TCG: coarse depth i in DRAW order (bins of the pdf)
+    auto tc_of = [&](int i) -> float { if constexpr (TCG) return tc_raw(i); else return tcA[i * 32 + j]; };
     bool wave_unsorted = false;  // TCG: some ray of this wave has two neighbouring stratified depths out of order
     bool bad_order = false;      // TCG: disorder beyond neighbours somewhere in this RAY (jitter outside [0, 1))
     bool wave_bad = false;       //      ... somewhere in this wave
-    // coarse depth of sorted RANK i (what the stable sort of renderer.py:289-301 puts there): the draw-order value itself unless
-    // the wave saw a reversed pair — then the neighbour that rounding swapped in, or (jitter outside [0, 1): never from
-    // torch.rand_like) the rank-i element of the row by counting, O(Sc^2) jitter reads per access: slow, exact, and not a
-    // path any renderer.py call reaches
-    auto tc_sorted = [&](int i) -> float {
-        float a = tc_raw(i);
-        if (wave_unsorted) {  // wave-uniform
-            if (!wave_bad) {
-                const float lo = i > 0 ? tc_raw(i - 1) : -__builtin_inff(), hi = i < Sc - 1 ? tc_raw(i + 1) : __builtin_inff();
-                a = lo > a ? lo : (a > hi ? hi : a);
-            } else {
-                for (int c = 0; c < Sc; ++c) {
-                    const float tv = tc_raw(c);
-                    int r = 0;
-                    for (int x = 0; x < Sc; ++x) {
-                        const float tx = tc_raw(x);
-                        r += (tx < tv || (tx == tv && x < c)) ? 1 : 0;
-                    }
-                    a = (r == i) ? tv : a;
-                }
-            }
-        }
-        return a;
-    };
+    auto tc_sorted = [&](int i) -> float { return p3d_coarse_rank(tc_raw, i, Sc, wave_unsorted, wave_bad); };
     uint32_t mw0 = 0u, mw1 = 0u, mw2 = 0u;  // TCG: known-masked bits of coarse samples 0-31 / 32-63 / 64-95 (registers, not LDS rows)
     uint32_t fw0 = 0u, fw1 = 0u, fw2 = 0u;  // TCG: sorted fine sample k is cropped (sigma = -1000 by position)
     const bool dump = DUMP && active && h == 0;
 
-    // ---- sample_stratified: renderer.py:320-324
+    // ---- stratified depths (TCG: made in the coarse pass, never stored)
     bool unsorted = false;
     float tcmin = __builtin_inff(), tcmax = -__builtin_inff();  // extrema of the coarse depths
     if constexpr (!TCG) {
-        const float step = (p.ray_end - p.ray_start) / (float)(Sc - 1);
-        const float* jit = p.jitter + ray * Sc;
-        // per-ray limits (ray_start = ray_end = 'auto'): math_utils.linspace + per-ray depth_delta (renderer.py:317-319)
-        const bool limits = p.ray_start_arr != nullptr;
-        const float rs = limits ? p.ray_start_arr[ray] : 0.0f, span = limits ? p.ray_end_arr[ray] - rs : 0.0f;
-        const float rdelta = span / (float)(Sc - 1);
         float prev = -__builtin_inff();
         for (int i0 = 0; i0 < Sc; i0 += 8) {  // eight loads of the jitter row in flight (one at a time exposed a global-load latency per sample)
             float jv[8];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int iq = i0 + q < Sc ? i0 + q : Sc - 1;
-                jv[q] = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 0u, ray, iq) : jit[iq];
-            }
+            for (int q = 0; q < 8; ++q) jv[q] = cx.jitter(i0 + q < Sc ? i0 + q : Sc - 1);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int i = i0 + q;
                 if (i < Sc) {  // wave-uniform
-                    float lin = (i < Sc / 2) ? p3d_fma(step, (float)i, p.ray_start) : p3d_fma(-step, (float)(Sc - 1 - i), p.ray_end);
-                    float t = lin + jv[q] * p.depth_delta;
-                    if (limits) {  // wave-uniform
-                        const float prod = ((float)i / (float)(Sc - 1)) * span;
-                        t = (rs + prod) + jv[q] * rdelta;
-                    } else if (p.disparity) {  // renderer.py:309-316: uniform in 1 / depth; p.ray_start / ray_end hold the reciprocals
-                        const float s01 = 1.0f / (float)(Sc - 1);
-                        const float l01 = (i < Sc / 2) ? p3d_fma(s01, (float)i, 0.0f) : p3d_fma(-s01, (float)(Sc - 1 - i), 1.0f);
-                        const float dd = l01 + jv[q] * p.depth_delta;
-                        const float ta_ = p.ray_start * (1.0f - dd), tb_ = p.ray_end * dd;
-                        t = 1.0f / (ta_ + tb_);
-                    }
+                    const float t = p3d_stratified_depth(i, Sc, jv[q], sp);
                     tcA[i * 32 + j] = t;
                     unsorted |= (t < prev);
                     prev = t;
@@ -599,22 +389,20 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     float tmin = __builtin_inff(), tmax = -__builtin_inff();
     if (Sf > 0) {
         // ---- coarse pass, densities only -> ray-marcher weights: renderer.py:179-211
-        MarchState st;
-        st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
+        MarchState st = p3d_march_start();
         uint32_t mword = 0;  // bit i & 31: coarse sample i is KNOWN to carry sigma = -1000 (cropped, or really decoded and masked)
         if constexpr (TCG) {
-            // stratified depths and coarse pass in one loop: the jitter row is read eight values at a time, the depths never
-            // reach LDS
+            // stratified depths and coarse pass in one loop: the jitter row is read eight values at a time, the depths never reach LDS
             float prev = -__builtin_inff(), pmax = -__builtin_inff();  // previous depth; maximum of all depths before it
             for (int i0 = 0; i0 < Sc; i0 += 8) {
                 float jv[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) jv[q] = jit_at(i0 + q < Sc ? i0 + q : Sc - 1);
+                for (int q = 0; q < 8; ++q) jv[q] = cx.jitter(i0 + q < Sc ? i0 + q : Sc - 1);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int i = i0 + q;
                     if (i >= Sc) break;  // wave-uniform
-                    const float t = depth_of(i, jv[q]);
+                    const float t = p3d_stratified_fixed(i, Sc, jv[q], sp);
                     unsorted |= (t < prev);
                     bad_order |= (t < pmax);
                     pmax = __builtin_fmaxf(pmax, prev);
@@ -623,22 +411,19 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     tcmax = __builtin_fmaxf(tcmax, t);
                     const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;  // renderer.py:179
                     float sigma = P3D_SIGMA_MASKED;
-                    const bool cropped = f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit);
+                    const bool cropped = cx.cropped(px, pz);
                     const bool live = !(cropped || st.Td < 1e-60);
                     const bool skip = __builtin_amdgcn_ballot_w64(live) == 0;
                     if (!skip) {
                         f32x16 dummy;
-                        p3d_decode_wave<false, true>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
+                        p3d_decode_wave<false, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
                     }
                     mword |= (cropped || (live && sigma == P3D_SIGMA_MASKED)) ? (1u << (i & 31)) : 0u;
                     if ((i & 31) == 31 || i == Sc - 1) {  // wave-uniform
                         if ((i >> 5) == 0) mw0 = mword; else if ((i >> 5) == 1) mw1 = mword; else mw2 = mword;
                         mword = 0;
                     }
-                    if (i > 0) {
-                        float tm;
-                        wcA[(i - 1) * 32 + j] = p3d_march_weight(st, t, sigma, tm);
-                    }
+                    if (i > 0) wcA[(i - 1) * 32 + j] = p3d_march_interval(st, t, sigma).w;
                     st.prev_t = t; st.prev_sigma = sigma;
                     ndec += skip ? 0 : 1;
                 }
@@ -650,13 +435,13 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             float sigma = P3D_SIGMA_MASKED;
             bool skip = false, live = true, cropped = false;
             if (early) {
-                cropped = f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit);
+                cropped = cx.cropped(px, pz);
                 live = !(cropped || st.Td < 1e-60);  // a cropped sample is -1000 by position; a dead ray's weights are 0
                 skip = __builtin_amdgcn_ballot_w64(live) == 0;
             }
             if (!skip) {
                 f32x16 dummy;
-                p3d_decode_wave<false, true>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
+                p3d_decode_wave<false, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
             }
             if (early) {  // a lane whose gathers were suppressed (dead ray) decoded garbage: its sample is NOT known to be masked
                 mword |= (cropped || (live && sigma == P3D_SIGMA_MASKED)) ? (1u << (i & 31)) : 0u;
@@ -664,8 +449,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             }
             if constexpr (DUMP) if (dump && p.dumps.sigma_coarse) p.dumps.sigma_coarse[ray * Sc + i] = sigma;
             if (i > 0) {
-                float tm;
-                float w = p3d_march_weight(st, t, sigma, tm);
+                float w = p3d_march_interval(st, t, sigma).w;
                 wcA[(i - 1) * 32 + j] = w;
                 if constexpr (DUMP) if (dump && p.dumps.weights_coarse) p.dumps.weights_coarse[ray * (Sc - 1) + i - 1] = w;
             }
@@ -673,92 +457,53 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             if constexpr (!DUMP) ndec += skip ? 0 : 1;
         }
         P3D_PHASE(P3D_PH_COARSE);
-        // ---- sample_importance / sample_pdf: renderer.py:328-387 (per ray; the cdf by both halves, the draws and the sort shared out: p3d_importance.hpp)
+        // ---- pdf -> cdf (per ray; by both halves — the draws and the sort are shared out: p3d_importance.hpp)
         const int Ns = Sc - 3;
-        {
-            // v[jj] = ws[jj+1] + 1e-5, ws[q] = (max(w[q-1],w[q]) + max(w[q],w[q+1])) * 0.5 + 0.01 ; stored at row jj+1
-            double sum = 0.0;
-            float wa = wcA[0 * 32 + j], wb = wcA[1 * 32 + j];
-            for (int jj = 0; jj < Ns; ++jj) {
-                float wc = wcA[(jj + 2) * 32 + j];
-                float m1 = __builtin_fmaxf(wa, wb), m2 = __builtin_fmaxf(wb, wc);
-                float v = ((m1 + m2) * 0.5f + 0.01f) + 1e-5f;
-                sum += (double)v;
-                wcA[(jj + 1) * 32 + j] = v;
-                wa = wb; wb = wc;
-            }
-            float fsum = (float)sum;
-            double acc = 0.0;
-            wcA[j] = 0.0f;  // cdf[0]
-            for (int jj = 0; jj < Ns; ++jj) {
-                float pdf = wcA[(jj + 1) * 32 + j] / fsum;
-                acc += (double)pdf;
-                wcA[(jj + 1) * 32 + j] = (float)acc;  // cdf[jj+1]
-            }
-        }
+        p3d_pdf_to_cdf<32>(wcA, Ns, j);
         P3D_PHASE(P3D_PH_CDF);
-        const float* uu = p.u + ray * Sf;
-        constexpr int DB = 8;  // draws in flight
+        // ---- draws, sort
+        constexpr int DB = P3D_DRAW_BATCH;
+        auto dump_draw = [&](bool mine, int i, float v, int k) {
+            if constexpr (DUMP) {
+                if (mine && p.dumps.depths_fine) p.dumps.depths_fine[ray * Sf + i] = v;
+                if (mine && p.dumps.inds) p.dumps.inds[ray * Sf + i] = k;
+            }
+        };
         if constexpr (P3D_NF_EXACT(NF)) {
             // Half h makes the draws [h * H, (h + 1) * H), sorts them, and after one cross-half exchange and a local merge holds
             // H of the sorted ranks (p3d_importance.hpp): half 1 rank H + i in register i, half 0 MINUS rank H - 1 - i.
-            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
             constexpr int H = NF / 2;
             static_assert(H % DB == 0, "whole batches of draws per half");
             const int d0 = h * H;
-            const uint32_t neg1 = h ? 0x80000000u : 0u, neg0 = h ? 0u : 0x80000000u;  // the sign bit in half 1 / in half 0
             float tf[H];
 #pragma unroll
-            for (int i = 0; i < H; ++i)  // every load of the half row issued before the first search
-                tf[i] = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, d0 + i) : uu[d0 + i];
+            for (int i = 0; i < H; ++i) tf[i] = cx.u(d0 + i);  // every load of the half row issued before the first search
 #pragma unroll
             for (int i0 = 0; i0 < H; i0 += DB) {
                 float ub[DB], vb[DB];
                 int kb[DB];
 #pragma unroll
                 for (int q = 0; q < DB; ++q) ub[q] = tf[i0 + q];
-                if constexpr (TCG) p3d_inverse_cdf<DB, 32>(wcA, tc_raw, Ns, j, ub, vb, kb);
-                else p3d_inverse_cdf<DB, 32>(wcA, tc_lds, Ns, j, ub, vb, kb);
+                p3d_inverse_cdf<DB, 32>(wcA, tc_of, Ns, j, ub, vb, kb);
 #pragma unroll
                 for (int q = 0; q < DB; ++q) {
                     tf[i0 + q] = vb[q];
-                    if constexpr (DUMP) {  // each half writes the entries of its own draws
-                        if (active && p.dumps.depths_fine) p.dumps.depths_fine[ray * Sf + d0 + i0 + q] = vb[q];
-                        if (active && p.dumps.inds) p.dumps.inds[ray * Sf + d0 + i0 + q] = kb[q];
-                    }
+                    dump_draw(active, d0 + i0 + q, vb[q], kb[q]);  // each half writes the entries of its own draws
                 }
             }
             P3D_PHASE(P3D_PH_DRAWS);
-#pragma unroll
-            for (int i = 0; i < H; ++i) tf[i] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tf[i]) ^ neg1);  // half 1 sorts descending
-            p3d_sort_network<H>(tf);
-#pragma unroll
-            for (int i = 0; i < H; i += 2) {
-                // v_permlane32_swap: afterwards lanes 0-31 hold key i of both halves (x: half 0's, y: half 1's), lanes 32-63 key i + 1;
-                // the second swap hands half 0 its (negated) minima and half 1 its maxima back, for both keys
-                u32x2 in = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, tf[i]), __builtin_bit_cast(uint32_t, tf[i + 1]), false, false);
-                const uint32_t in0 = in.x, in1 = in.y;  // (scalars first: a bit cast of a vector ELEMENT reads element 0)
-                float mn_neg, mx;
-                p3d_cross_half_exchange(__builtin_bit_cast(float, in0), __builtin_bit_cast(float, in1), mn_neg, mx);
-                u32x2 out = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, mn_neg), __builtin_bit_cast(uint32_t, mx), false, false);
-                const uint32_t out0 = out.x, out1 = out.y;
-                tf[i] = __builtin_bit_cast(float, out0);
-                tf[i + 1] = __builtin_bit_cast(float, out1);
-            }
-            p3d_valley_merge<H>(tf);
+            p3d_sort_halves<H>(tf, h);
             // over the cdf rows: every search of BOTH halves is done, and the other half's rows are read below — same wave, so
             // ordering the wave's own LDS operations is all it takes
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             const int row0 = p3d_half_rank(H, h, 0), rstep = h ? 1 : -1;
+            const uint32_t neg0 = h ? 0u : 0x80000000u;  // half 0 holds its keys negated
             uint64_t crop = 0ull;  // TCG: bit i = the key of register i is cropped
 #pragma unroll
             for (int i = 0; i < H; ++i) {
                 const float v = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tf[i]) ^ neg0);
                 tfA[(row0 + rstep * i) * 32 + j] = v;
-                if constexpr (TCG) {
-                    const float px = ox + v * dx, pz = oz + v * dz;
-                    crop |= (f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit)) ? (1ull << i) : 0ull;
-                }
+                if constexpr (TCG) crop |= cx.cropped_at(v) ? (1ull << i) : 0ull;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             if constexpr (TCG) {  // register i -> rank: half 1 shifts by H, half 0 mirrors; then each half takes the other's bits
@@ -768,10 +513,11 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 fw0 |= __shfl_xor(fw0, 32); fw1 |= __shfl_xor(fw1, 32); fw2 |= __shfl_xor(fw2, 32);
             }
         } else if constexpr (NF > 0) {  // the padded capacity (NF = 64): both halves do all of it
+            // (the same text as k_render_slots' below, on purpose: behind one shared helper every LDS read of the searches got one
+            // more VALU operation in front of it, +260-370 instructions per kernel, profiles/r08_resource_*.txt)
             float tf[NF];
 #pragma unroll
-            for (int i = 0; i < NF; ++i)  // every load of the row issued before the first search
-                tf[i] = (i < Sf) ? (p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i]) : 0.0f;
+            for (int i = 0; i < NF; ++i) tf[i] = (i < Sf) ? cx.u(i) : 0.0f;  // every load of the row issued before the first search
 #pragma unroll
             for (int i0 = 0; i0 < NF; i0 += DB) {
                 if (i0 < Sf) {  // wave-uniform
@@ -779,15 +525,11 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     int kb[DB];
 #pragma unroll
                     for (int q = 0; q < DB; ++q) ub[q] = tf[i0 + q];
-                    if constexpr (TCG) p3d_inverse_cdf<DB, 32>(wcA, tc_raw, Ns, j, ub, vb, kb);
-                    else p3d_inverse_cdf<DB, 32>(wcA, tc_lds, Ns, j, ub, vb, kb);
+                    p3d_inverse_cdf<DB, 32>(wcA, tc_of, Ns, j, ub, vb, kb);
 #pragma unroll
                     for (int q = 0; q < DB; ++q) {
                         tf[i0 + q] = (i0 + q < Sf) ? vb[q] : __builtin_inff();
-                        if constexpr (DUMP) {
-                            if (dump && i0 + q < Sf && p.dumps.depths_fine) p.dumps.depths_fine[ray * Sf + i0 + q] = vb[q];
-                            if (dump && i0 + q < Sf && p.dumps.inds) p.dumps.inds[ray * Sf + i0 + q] = kb[q];
-                        }
+                        if (i0 + q < Sf) dump_draw(dump, i0 + q, vb[q], kb[q]);
                     }
                 } else {
 #pragma unroll
@@ -801,8 +543,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 if (i < Sf) {
                     tfA[i * 32 + j] = tf[i];  // over the cdf rows: every search is done
                     if constexpr (TCG) {
-                        const float px = ox + tf[i] * dx, pz = oz + tf[i] * dz;
-                        const uint32_t b = (f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit)) ? (1u << (i & 31)) : 0u;
+                        const uint32_t b = cx.cropped_at(tf[i]) ? (1u << (i & 31)) : 0u;
                         if (i < 32) fw0 |= b; else if (i < 64) fw1 |= b; else fw2 |= b;
                     }
                 }
@@ -811,19 +552,13 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 float ub[DB], vb[DB];
                 int kb[DB];
 #pragma unroll
-                for (int q = 0; q < DB; ++q) {
-                    const int iq = i0 + q < Sf ? i0 + q : Sf - 1;
-                    ub[q] = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, iq) : uu[iq];
-                }
-                p3d_inverse_cdf<DB, 32>(wcA, tc_lds, Ns, j, ub, vb, kb);
+                for (int q = 0; q < DB; ++q) ub[q] = cx.u(i0 + q < Sf ? i0 + q : Sf - 1);
+                p3d_inverse_cdf<DB, 32>(wcA, tc_of, Ns, j, ub, vb, kb);
 #pragma unroll
                 for (int q = 0; q < DB; ++q) {
                     if (i0 + q < Sf) {
                         tfA[(i0 + q) * 32 + j] = vb[q];
-                        if constexpr (DUMP) {
-                            if (dump && p.dumps.depths_fine) p.dumps.depths_fine[ray * Sf + i0 + q] = vb[q];
-                            if (dump && p.dumps.inds) p.dumps.inds[ray * Sf + i0 + q] = kb[q];
-                        }
+                        dump_draw(dump, i0 + q, vb[q], kb[q]);
                     }
                 }
             }
@@ -845,25 +580,10 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             }
         }
     }
-    // ---- final pass: merge on the fly (ties: coarse first = stable), decode, composite [rgb | xyz]:
-    //      renderer.py:243-259, ray_marcher.py:25-57.
-    // Every lane walks ITS OWN merged list.  With the early-outs on, a lane first consumes — without a decode — every sample
-    // whose sigma = -1000 is already known (cropped by position, or a coarse sample the coarse pass really decoded and found
-    // masked) while the previous sample's sigma is <= 602: the interval's softplus argument is then <= -200, rho = alpha = w = 0
-    // and Td * (double)(1.0f + 1e-10f) = Td, i.e. the marcher update is exactly the identity (include/p3d_numerics.h); only
-    // prev_t / prev_sigma move.  A dead ray (Td < 1e-60: every later weight is exactly 0) drops all its remaining samples.
-    // The merge itself runs ONCE, ahead of the walk, as a uniform loop that leaves two bit rows per lane in LDS (merged sample q
-    // is coarse / is known); the walk then jumps over a whole run of known samples with a count-trailing-ones — consuming them
-    // one at a time was a chain of two LDS round trips per sample and a quarter of the kernel (profiles/history/r02_notes.txt).
-    // What is left — the samples that can matter — is decoded one per wave-step until every lane has finished, so a tile of
-    // rays that miss the subject runs ~Sf/2 steps instead of Sc + Sf.  A consumed sample's colour is fetched after all if one
-    // of its interval weights turns out non-zero (sigma of a neighbour >= ~794): results are bit-identical by construction.
-    MarchState st;
-    st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
-    f32x16 C, prev_rgb;
-    float Cx = 0.0f, Cy = 0.0f, Cz = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) { C[c] = 0.0f; prev_rgb[c] = 0.0f; }
+    // ---- final pass: merge pre-pass, then the walk (see the comment above the kernel)
+    MarchState st = p3d_march_start();
+    P3dAccum acc;
+    f32x16 prev_rgb = 0.0f;
     {
         int ci = 0, fi = 0;
         float ta = TCG ? 0.0f : tcA[j], tb = (Sf > 0) ? tfA[j] : __builtin_inff();
@@ -872,10 +592,6 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
         tmax = __builtin_fmaxf(tcmax, (Sf > 0) ? tfA[(Sf - 1) * 32 + j] : -__builtin_inff());
         bool prev_skipped = false, first = true, done = false;
         int m = 0;  // samples of this lane consumed so far (position in the merged list)
-        auto is_cropped = [&](float t) {
-            const float px = ox + t * dx, pz = oz + t * dz;
-            return f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit);
-        };
         auto advance = [&](bool take_c) {  // pop the head of the coarse or of the fine list
             ci += take_c ? 1 : 0;
             fi += take_c ? 0 : 1;
@@ -888,62 +604,13 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
         };
         float tcn = 0.0f;  // TCG: the head of the coarse list, tc_sorted(min(ci, Sc - 1)), fetched ahead of its use
         if constexpr (TCG) {
-            // the merge without a coarse column: coarse rank i lands at merged position i + #{fine < t_i} (ties: coarse first),
-            // found by a search in the sorted fine column, eight ranks in flight; the two bit rows are built in registers (six
-            // words each: Sc + Sf <= 192) and stored once
-            uint32_t slw[6], knw[6];
-#pragma unroll
-            for (int w = 0; w < 6; ++w) { slw[w] = 0u; knw[w] = 0u; }
-            const int Sch = ((Sc + 15) >> 4) << 3, ib = h * Sch;  // half h searches the coarse ranks [h * Sch, (h + 1) * Sch)
-            for (int i0 = 0; i0 < Sch; i0 += 8) {
-                float tv[8];
-                int pos[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { tv[q] = tc_sorted(ib + i0 + q < Sc ? ib + i0 + q : Sc - 1); pos[q] = 0; }
-#pragma unroll
-                for (int step = 64; step >= 1; step >>= 1) {
-                    float c[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) c[q] = tfA[((pos[q] + step <= Sf) ? pos[q] + step - 1 : 0) * 32 + j];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) pos[q] = ((pos[q] + step <= Sf) && (c[q] < tv[q])) ? pos[q] + step : pos[q];
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int i = ib + i0 + q;
+            p3d_merge_bits_ranks(
+                tc_sorted, [&](int k) { return tfA[k * 32 + j]; },
+                [&](int i, float t) {
                     const uint32_t mwv = (i < 32) ? mw0 : (i < 64 ? mw1 : mw2);
-                    const bool known = is_cropped(tv[q]) || ((mwv >> (i & 31)) & 1u);
-                    const int P = i + pos[q], pw = (i < Sc) ? (P >> 5) : -1;  // (a rank past the end sets no bit)
-                    const uint32_t b = 1u << (P & 31);
-#pragma unroll
-                    for (int w = 0; w < 6; ++w) {
-                        slw[w] |= (pw == w) ? b : 0u;
-                        knw[w] |= (pw == w && known) ? b : 0u;
-                    }
-                }
-            }
-#pragma unroll
-            for (int w = 0; w < 6; ++w) { slw[w] |= __shfl_xor(slw[w], 32); knw[w] |= __shfl_xor(knw[w], 32); }  // the other half's ranks
-            // cropped fine samples: fine k sits at the k-th zero of the is-coarse row
-            if (__builtin_amdgcn_ballot_w64((fw0 | fw1 | fw2) != 0u) != 0) {
-                int fk = 0;
-#pragma unroll
-                for (int w = 0; w < 6; ++w) {
-                    if (w * 32 < S) {  // wave-uniform
-                        uint32_t kk = 0u;
-                        for (int b = 0; b < 32; ++b) {
-                            const bool isf = !((slw[w] >> b) & 1u) && (w * 32 + b < S);
-                            const uint32_t fwv = (fk < 32) ? fw0 : (fk < 64 ? fw1 : fw2);
-                            kk |= (isf && ((fwv >> (fk & 31)) & 1u)) ? (1u << b) : 0u;
-                            fk += isf ? 1 : 0;
-                        }
-                        knw[w] |= kk;
-                    }
-                }
-            }
-#pragma unroll
-            for (int w = 0; w < 6; ++w)
-                if (w < nmw) { knA[w * 32 + j] = knw[w]; slA[w * 32 + j] = slw[w]; }
+                    return cx.cropped_at(t) || ((mwv >> (i & 31)) & 1u);
+                },
+                [&](int w, uint32_t kw, uint32_t sw) { knA[w * 32 + j] = kw; slA[w * 32 + j] = sw; }, fw0, fw1, fw2, Sc, Sf, h);
             tcn = tc_sorted(0);
         } else
         if constexpr (EARLY) {
@@ -956,7 +623,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             p3d_merge_bits_half(
                 [&](bool c, int i) { return (c ? tcA : tfA)[i * 32 + j]; },
                 [&](bool c, int i, float t) {
-                    bool known = is_cropped(t);
+                    bool known = cx.cropped_at(t);
                     if (c && Sf > 0) known = known || ((mkA[(i >> 5) * 32 + j] >> (i & 31)) & 1u);  // Sf == 0: no coarse pass ran
                     return known;
                 },
@@ -1026,15 +693,13 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             const bool have = EARLY ? !done : true;
             const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;
             float sigma = P3D_SIGMA_MASKED;
-            f32x16 rgb;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) rgb[c] = 0.0f;
+            f32x16 rgb = 0.0f;
             const bool live = have && !known;
             bool skipped = true;
             if (__builtin_amdgcn_ballot_w64(live) != 0) {
                 bool have_rgb;  // EARLY: colour on demand (p3d_decode.hpp, LAZY): a step whose live samples are all masked has none
-                if constexpr (FAST) have_rgb = p3d_decode_wave_fast<true, true, EARLY, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
-                else have_rgb = p3d_decode_wave<true, true, EARLY>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
+                if constexpr (FAST) have_rgb = p3d_decode_wave_fast<true, true, EARLY, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
+                else have_rgb = p3d_decode_wave<true, true, EARLY>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
                 if constexpr (!DUMP) ndec += 1;
                 skipped = !live || !have_rgb;  // per lane: a lane whose gathers were suppressed has no colour
                 if (known) sigma = P3D_SIGMA_MASKED;
@@ -1046,35 +711,12 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             }
             // (the guard decodes below are wave-level operations: every lane must reach them, also the ones without a sample)
             const bool marching = have && !first;
-            float w = 0.0f, tm = 0.0f;
-            if (marching) w = p3d_march_weight(st, t, sigma, tm);
+            P3dInterval iv = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (marching) iv = p3d_march_interval(st, t, sigma);
             const float ppx = ox + st.prev_t * dx, ppy = oy + st.prev_t * dy, ppz = oz + st.prev_t * dz;
-            if (early) {  // exactness guard: a skipped endpoint whose interval weight is non-zero needs its real colour
-                if (__builtin_amdgcn_ballot_w64(marching && prev_skipped && w != 0.0f) != 0) {
-                    float s2;
-                    f32x16 c2;
-                    if constexpr (FAST) p3d_decode_wave_fast<true, true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
-                    else p3d_decode_wave<true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
-                    if (prev_skipped) prev_rgb = c2;
-                    prev_skipped = false;
-                }
-                if (__builtin_amdgcn_ballot_w64(marching && skipped && w != 0.0f) != 0) {
-                    float s2;
-                    if constexpr (FAST) p3d_decode_wave_fast<true, true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
-                    else p3d_decode_wave<true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
-                    skipped = false;
-                }
-            }
+            if (early) p3d_guard_colours<FAST>(lds, cx, marching, iv.w, prev_skipped, prev_rgb, ppx, ppy, ppz, skipped, rgb, px, py, pz);
             if (have) {
-                if (!first) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) C[c] = p3d_fma(w, (prev_rgb[c] + rgb[c]) * 0.5f, C[c]);
-                    Cx = p3d_fma(w, (ppx + px) * 0.5f, Cx);
-                    Cy = p3d_fma(w, (ppy + py) * 0.5f, Cy);
-                    Cz = p3d_fma(w, (ppz + pz) * 0.5f, Cz);
-                    st.W = st.W + w;
-                    st.D = p3d_fma(w, tm, st.D);
-                }
+                if (!first) p3d_composite_interval<false>(acc, st, iv, prev_rgb, rgb, ppx, ppy, ppz, px, py, pz);
                 st.prev_t = t; st.prev_sigma = sigma;
                 prev_rgb = rgb;
                 prev_skipped = skipped;
@@ -1084,49 +726,12 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             P3D_PHASE(P3D_PH_MARCH);
         }
     }
-    // ---- outputs.  white_back and the [-1,1] rescale are per ray (ray_marcher.py:52-55); the depth clamp is global.
-    {
-        const float Wt = st.W;
-        float d = st.D / Wt;
-        if (d != d) d = __builtin_inff();  // nan_to_num(nan=inf): ray_marcher.py:49
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            float v = C[c];
-            if (p.white_back) v = (v + 1.0f) - Wt;
-            C[c] = v * 2.0f - 1.0f;
-        }
-        if (p.white_back) { Cx = (Cx + 1.0f) - Wt; Cy = (Cy + 1.0f) - Wt; Cz = (Cz + 1.0f) - Wt; }
-        Cx = Cx * 2.0f - 1.0f; Cy = Cy * 2.0f - 1.0f; Cz = Cz * 2.0f - 1.0f;
-        if (active) {
-            float* dst = p.out_feat + ray * 32 + 4 * h;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *(f32x4*)(dst + 8 * q) = (f32x4){C[4 * q], C[4 * q + 1], C[4 * q + 2], C[4 * q + 3]};
-            if (h == 0) {
-                p.out_depth[ray] = d;  // clamped by k_render_finish
-                p.out_wsum[ray] = Wt;  // weights.sum(2): renderer.py:264
-                p.out_xyz[ray * 3] = Cx; p.out_xyz[ray * 3 + 1] = Cy; p.out_xyz[ray * 3 + 2] = Cz;
-                if constexpr (DUMP) if (p.dumps.depth_unclamped) p.dumps.depth_unclamped[ray] = st.D / Wt;
-            }
-        }
-    }
-    // global min / max of all depths of the call (torch.min/max(depths): ray_marcher.py:50)
-    if (!active) { tmin = __builtin_inff(); tmax = -__builtin_inff(); }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        tmin = __builtin_fminf(tmin, __shfl_xor(tmin, o));
-        tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, o));
-    }
+    // ---- outputs (per ray; the depth clamp is global: k_render_finish), depth range
+    p3d_ray_outputs<false, DUMP>(p, ray, h, active, acc, st);
+    p3d_wave_minmax(active, tmin, tmax);
     P3D_PHASE(P3D_PH_OUT);
     P3D_PHASE_FLUSH();
-    if (lane == 0) {
-        atomicMin(p.gminmax, p3d_f2ord(tmin));
-        atomicMax(p.gminmax + 1, p3d_f2ord(tmax));
-        if (p.per_view_clamp) {  // a tile never straddles two views
-            atomicMin(p.gminmax + 4 + 2 * nlo, p3d_f2ord(tmin));
-            atomicMax(p.gminmax + 5 + 2 * nlo, p3d_f2ord(tmax));
-        }
-        if constexpr (!DUMP) atomicAdd((unsigned long long*)(p.gminmax + 2), (unsigned long long)ndec);  // wave-level decode steps
-    }
+    p3d_depth_range_atomics<!DUMP>(p, cx.nlo, lane, tmin, tmax, ndec);
 }
 
 // v of lane ^ X within each half-wave (X < 32): ds_swizzle in bit mode (and 0x1f, or 0, xor X) — the crossbar, no address VGPR
@@ -1192,30 +797,12 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
     long long tile = (long long)blockIdx.x * nwaves + wave;  // RPW-ray tiles
     if (tile >= p.ntiles) return;  // no workgroup barrier below this line
     float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * RS;
-
     const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
-    long long n = tile / p.tiles_per_img, tl = tile - n * p.tiles_per_img;
-    long long r;
-    if (p.tile_w > 0) {  // 4 x (RPW / 4) pixel tile, Morton lane order (a lane quad = a 2x2 pixel block: the quad-cooperative gathers)
-        long long ty = tl / p.tiles_x, tx = tl - ty * p.tiles_x;
-        const int lx = (jr & 1) | ((jr >> 1) & 2), ly = ((jr >> 1) & 1) | ((jr >> 2) & 2);
-        r = (ty * (RPW / 4) + ly) * p.tile_w + tx * 4 + lx;
-    } else {
-        r = tl * RPW + jr;
-    }
-    const bool active = r < p.R;
-    const long long rc = active ? r : p.R - 1;
-    const size_t ray = (size_t)n * p.R + rc;
-
-    P3dPlaneGeom g;
-    g.halfW = 0.5f * (float)p.W; g.halfH = 0.5f * (float)p.H; g.fW = (float)p.W; g.fH = (float)p.H; g.W = p.W;
-    g.plane_bytes = (uint32_t)p.H * (uint32_t)p.W * 128u;
-    unsigned nlo = __builtin_amdgcn_readfirstlane((unsigned)n);
-    const float* pbase = p.planes + ((p.cfg.flags & P3D_FLAG_SHARED_PLANES) ? (size_t)0 : (size_t)nlo * 3 * (g.plane_bytes / 4));
-    auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)pbase, 0, 3 * g.plane_bytes, 0x00020000);
-    const P3dDecodeCfg cfg = p.cfg;
-    const bool early = !(cfg.flags & P3D_FLAG_NO_EARLY_OUT);
-    const bool f_crop = (cfg.flags & P3D_FLAG_CROP) != 0;
+    const P3dRayCtx cx = p3d_ray_setup(p, p3d_slots_tile_ray<RPW>(p, tile, jr), Sc, Sf);
+    const bool active = cx.active;
+    const size_t ray = cx.ray;
+    const float ox = cx.ox, oy = cx.oy, oz = cx.oz, dx = cx.dx, dy = cx.dy, dz = cx.dz;
+    const bool early = !(cx.cfg.flags & P3D_FLAG_NO_EARLY_OUT);
     int ndec = 0;
     // xk = v of the lane whose slot differs by k (lane ^ RPW k; x2, x3: four slots only).  Scalars rather than an array, and
     // of_slot's select tree rather than p3d_select's: with those the four-slot instantiations spilled SGPRs or allocated scratch.
@@ -1232,9 +819,6 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
         return (k & 1) ? ((k & 2) ? s.x3 : s.x1) : ((k & 2) ? s.x2 : s.x0);
     };
 
-    const float ox = p.rays_o[ray * 3], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
-    const float dx = p.rays_d[ray * 3], dy = p.rays_d[ray * 3 + 1], dz = p.rays_d[ray * 3 + 2];
-
     // LDS rows of this wave: row(i)[jr]; all slots of a ray write the same values
     float* tcA = wl;
     float* wcA = tcA + Sc * RS;
@@ -1243,39 +827,19 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
 
     bool unsorted = false;
     {
-        const float step = (p.ray_end - p.ray_start) / (float)(Sc - 1);
-        const float* jit = p.jitter + ray * Sc;
-        const bool limits = p.ray_start_arr != nullptr;  // per-ray limits: as in k_render
-        const float rs = limits ? p.ray_start_arr[ray] : 0.0f, span = limits ? p.ray_end_arr[ray] - rs : 0.0f;
-        const float rdelta = span / (float)(Sc - 1);
+        const P3dSpacing sp = p3d_spacing_of(p, ray, Sc);
         float prev = -__builtin_inff();
         for (int i = 0; i < Sc; ++i) {
-            float lin = (i < Sc / 2) ? p3d_fma(step, (float)i, p.ray_start) : p3d_fma(-step, (float)(Sc - 1 - i), p.ray_end);
-            const float ji = p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 0u, ray, i) : jit[i];
-            float t = lin + ji * p.depth_delta;
-            if (limits) {
-                const float prod = ((float)i / (float)(Sc - 1)) * span;
-                t = (rs + prod) + ji * rdelta;
-            } else if (p.disparity) {
-                const float s01 = 1.0f / (float)(Sc - 1);
-                const float l01 = (i < Sc / 2) ? p3d_fma(s01, (float)i, 0.0f) : p3d_fma(-s01, (float)(Sc - 1 - i), 1.0f);
-                const float dd = l01 + ji * p.depth_delta;
-                const float ta_ = p.ray_start * (1.0f - dd), tb_ = p.ray_end * dd;
-                t = 1.0f / (ta_ + tb_);
-            }
+            const float t = p3d_stratified_depth(i, Sc, cx.jitter(i), sp);
             tcA[i * RS + jr] = t;
             unsorted |= (t < prev);
             prev = t;
         }
     }
     float tmin = __builtin_inff(), tmax = -__builtin_inff();
-    auto is_cropped = [&](float px, float pz) {
-        return f_crop && (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit);
-    };
     if (Sf > 0) {
         // ---- coarse pass, SLOTS samples per step
-        MarchState st;
-        st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
+        MarchState st = p3d_march_start();
         for (int i = 0; i < Sc; i += SLOTS) {
             float tq[SLOTS];
 #pragma unroll
@@ -1285,12 +849,12 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
             float sigma = P3D_SIGMA_MASKED;
             bool skip = false, live = true;
             if (early) {
-                live = !(is_cropped(px, pz) || st.Td < 1e-60);  // slots > 0: Td before the step's first interval — conservative, still exact
+                live = !(cx.cropped(px, pz) || st.Td < 1e-60);  // slots > 0: Td before the step's first interval — conservative, still exact
                 skip = __builtin_amdgcn_ballot_w64(live) == 0;
             }
             if (!skip) {
                 f32x16 dummy;
-                p3d_decode_wave<false, true>(lds, rs, g, cfg, px, py, pz, sigma, dummy, live);
+                p3d_decode_wave<false, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
                 ndec += 1;
             }
             const Slots sx = exchange(sigma);
@@ -1298,43 +862,20 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
             for (int q = 0; q < SLOTS; ++q) {
                 if (i + q < Sc) {  // uniform
                     const float sq = of_slot(q, sx);
-                    if (i + q > 0) {
-                        float tm;
-                        wcA[(i + q - 1) * RS + jr] = p3d_march_weight(st, tq[q], sq, tm);
-                    }
+                    if (i + q > 0) wcA[(i + q - 1) * RS + jr] = p3d_march_interval(st, tq[q], sq).w;
                     st.prev_t = tq[q]; st.prev_sigma = sq;
                 }
             }
         }
+        // ---- pdf -> cdf, draws, sort
         const int Ns = Sc - 3;
-        {
-            double sum = 0.0;
-            float wa = wcA[0 * RS + jr], wb = wcA[1 * RS + jr];
-            for (int jj = 0; jj < Ns; ++jj) {
-                float wc = wcA[(jj + 2) * RS + jr];
-                float m1 = __builtin_fmaxf(wa, wb), m2 = __builtin_fmaxf(wb, wc);
-                float v = ((m1 + m2) * 0.5f + 0.01f) + 1e-5f;
-                sum += (double)v;
-                wcA[(jj + 1) * RS + jr] = v;
-                wa = wb; wb = wc;
-            }
-            float fsum = (float)sum;
-            double acc = 0.0;
-            wcA[jr] = 0.0f;
-            for (int jj = 0; jj < Ns; ++jj) {
-                float pdf = wcA[(jj + 1) * RS + jr] / fsum;
-                acc += (double)pdf;
-                wcA[(jj + 1) * RS + jr] = (float)acc;
-            }
-        }
-        const float* uu = p.u + ray * Sf;
+        p3d_pdf_to_cdf<RS>(wcA, Ns, jr);
         if constexpr (NF > 0) {
-            // as in k_render: every load of the row issued before the first search, eight draws in lock-step (the eight LDS
-            // reads of a search step in flight together; one draw at a time was a chain of 8 dependent LDS round trips x Sf)
-            constexpr int DB = 8;
+            // the padded capacity, k_render's text (see there why not one shared function): all loads first, eight draws in lock-step
             float tf[NF];
+            constexpr int DB = P3D_DRAW_BATCH;
 #pragma unroll
-            for (int i = 0; i < NF; ++i) tf[i] = (i < Sf) ? (p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i]) : 0.0f;
+            for (int i = 0; i < NF; ++i) tf[i] = (i < Sf) ? cx.u(i) : 0.0f;
 #pragma unroll
             for (int i0 = 0; i0 < NF; i0 += DB) {
                 if (i0 < Sf) {  // wave-uniform
@@ -1357,7 +898,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
         } else {
             // the generic path sorts in LDS: only slot 0 may move the keys (all slots of a ray share the column)
             for (int i = 0; i < Sf; ++i) {
-                const float ui[1] = {p.rng ? p3d_draw(p.seed_lo, p.seed_hi, 1u, ray, i) : uu[i]};
+                const float ui[1] = {cx.u(i)};
                 float v[1];
                 int k[1];
                 p3d_inverse_cdf<1, RS>(wcA, tc_lds, Ns, jr, ui, v, k);
@@ -1368,12 +909,10 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
         if (__builtin_amdgcn_ballot_w64(unsorted) != 0 && slot == 0 && h == 0) p3d_lds_insertion_sort<RS>(tcA, Sc, jr);
     }
     // ---- final pass: SLOTS merged samples per step
-    MarchState st;
-    st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = 0.0f; st.prev_sigma = 0.0f;
-    f32x16 C, prev_rgb;
-    float Cx = 0.0f, Cy = 0.0f, Cz = 0.0f, ppx = 0.0f, ppy = 0.0f, ppz = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) { C[c] = 0.0f; prev_rgb[c] = 0.0f; }
+    MarchState st = p3d_march_start();
+    P3dAccum acc;
+    f32x16 prev_rgb = 0.0f;
+    float ppx = 0.0f, ppy = 0.0f, ppz = 0.0f;
     {
         int ci = 0, fi = 0;
         float ta = tcA[jr], tb = (Sf > 0) ? tfA[jr] : __builtin_inff();
@@ -1394,33 +933,9 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
         // the second half of k_render's loop body, for one sample whose decode (or skip) has already happened
         auto consume = [&](int m, float t, float px, float py, float pz, float sigma, f32x16 rgb, bool skipped) {
             if (m > 0) {
-                float tm;
-                float w = p3d_march_weight(st, t, sigma, tm);
-                if (early && !WO) {
-                    if (__builtin_amdgcn_ballot_w64(prev_skipped && w != 0.0f) != 0) {
-                        float s2;
-                        f32x16 c2;
-                        if constexpr (FAST) p3d_decode_wave_fast<true, true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
-                        else p3d_decode_wave<true>(lds, rs, g, cfg, ppx, ppy, ppz, s2, c2);
-                        if (prev_skipped) prev_rgb = c2;
-                        prev_skipped = false;
-                    }
-                    if (__builtin_amdgcn_ballot_w64(skipped && w != 0.0f) != 0) {
-                        float s2;
-                        if constexpr (FAST) p3d_decode_wave_fast<true, true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
-                        else p3d_decode_wave<true>(lds, rs, g, cfg, px, py, pz, s2, rgb);
-                        skipped = false;
-                    }
-                }
-                if constexpr (!WO) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) C[c] = p3d_fma(w, (prev_rgb[c] + rgb[c]) * 0.5f, C[c]);
-                    Cx = p3d_fma(w, (ppx + px) * 0.5f, Cx);
-                    Cy = p3d_fma(w, (ppy + py) * 0.5f, Cy);
-                    Cz = p3d_fma(w, (ppz + pz) * 0.5f, Cz);
-                }
-                st.W = st.W + w;
-                st.D = p3d_fma(w, tm, st.D);
+                const P3dInterval iv = p3d_march_interval(st, t, sigma);
+                if (early && !WO) p3d_guard_colours<FAST>(lds, cx, true, iv.w, prev_skipped, prev_rgb, ppx, ppy, ppz, skipped, rgb, px, py, pz);
+                p3d_composite_interval<WO>(acc, st, iv, prev_rgb, rgb, ppx, ppy, ppz, px, py, pz);
             }
             st.prev_t = t; st.prev_sigma = sigma;
             prev_rgb = rgb;
@@ -1436,19 +951,17 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
             }
             const float px = p3d_select(pxq, slot), py = p3d_select(pyq, slot), pz = p3d_select(pzq, slot);
             float sigma = P3D_SIGMA_MASKED;
-            f32x16 rgb;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) rgb[c] = 0.0f;
+            f32x16 rgb = 0.0f;
             bool skipped = false, live = true;
             if (early) {
                 // exact mode: below 1e-60 every later weight is exactly 0.  Tolerance mode: the transmittance bounds what the rest
                 // of the ray can still add — stop at 2e-6, inside the 2e-5 budget (as in k_render)
-                live = !(is_cropped(px, pz) || st.Td < (FAST ? 2e-6 : 1e-60));
+                live = !(cx.cropped(px, pz) || st.Td < (FAST ? 2e-6 : 1e-60));
                 skipped = __builtin_amdgcn_ballot_w64(live) == 0;
             }
             if (!skipped) {
-                if constexpr (FAST) p3d_decode_wave_fast<!WO, true, false, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
-                else p3d_decode_wave<true, true>(lds, rs, g, cfg, px, py, pz, sigma, rgb, live);
+                if constexpr (FAST) p3d_decode_wave_fast<!WO, true, false, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
+                else p3d_decode_wave<true, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
                 ndec += 1;
                 skipped = !live;
             }
@@ -1468,46 +981,10 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
             }
         }
     }
-    {
-        const float Wt = st.W;
-        float d = st.D / Wt;
-        if (d != d) d = __builtin_inff();
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            float v = C[c];
-            if (p.white_back) v = (v + 1.0f) - Wt;
-            C[c] = v * 2.0f - 1.0f;
-        }
-        if (p.white_back) { Cx = (Cx + 1.0f) - Wt; Cy = (Cy + 1.0f) - Wt; Cz = (Cz + 1.0f) - Wt; }
-        Cx = Cx * 2.0f - 1.0f; Cy = Cy * 2.0f - 1.0f; Cz = Cz * 2.0f - 1.0f;
-        if (active && slot == 0) {
-            if constexpr (!WO) {
-                float* dst = p.out_feat + ray * 32 + 4 * h;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *(f32x4*)(dst + 8 * q) = (f32x4){C[4 * q], C[4 * q + 1], C[4 * q + 2], C[4 * q + 3]};
-            }
-            if (h == 0) {
-                p.out_depth[ray] = d;
-                p.out_wsum[ray] = Wt;
-                if constexpr (!WO) { p.out_xyz[ray * 3] = Cx; p.out_xyz[ray * 3 + 1] = Cy; p.out_xyz[ray * 3 + 2] = Cz; }
-            }
-        }
-    }
-    if (!active) { tmin = __builtin_inff(); tmax = -__builtin_inff(); }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        tmin = __builtin_fminf(tmin, __shfl_xor(tmin, o));
-        tmax = __builtin_fmaxf(tmax, __shfl_xor(tmax, o));
-    }
-    if (lane == 0) {
-        atomicMin(p.gminmax, p3d_f2ord(tmin));
-        atomicMax(p.gminmax + 1, p3d_f2ord(tmax));
-        if (p.per_view_clamp) {
-            atomicMin(p.gminmax + 4 + 2 * nlo, p3d_f2ord(tmin));
-            atomicMax(p.gminmax + 5 + 2 * nlo, p3d_f2ord(tmax));
-        }
-        atomicAdd((unsigned long long*)(p.gminmax + 2), (unsigned long long)ndec);
-    }
+    // ---- outputs (slot 0's lanes), depth range
+    p3d_ray_outputs<WO, false>(p, ray, h, active && slot == 0, acc, st);
+    p3d_wave_minmax(active, tmin, tmax);
+    p3d_depth_range_atomics<true>(p, cx.nlo, lane, tmin, tmax, ndec);
 }
 
 __global__ void k_minmax_init(uint32_t* g, int nviews) {
@@ -1542,11 +1019,8 @@ __global__ void k_stratified(float start, float end, float delta, int S, const f
                              float* __restrict__ out) {
     long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= NR) return;
-    const float step = (end - start) / (float)(S - 1);
-    for (int i = 0; i < S; ++i) {
-        float lin = (i < S / 2) ? p3d_fma(step, (float)i, start) : p3d_fma(-step, (float)(S - 1 - i), end);
-        out[r * S + i] = lin + jitter[r * S + i] * delta;
-    }
+    const P3dSpacing sp = p3d_spacing_fixed(start, end, delta, S);
+    for (int i = 0; i < S; ++i) out[r * S + i] = p3d_stratified_fixed(i, S, jitter[r * S + i], sp);
 }
 
 __global__ void k_minmax_decode(const uint32_t* g, float* out) {
@@ -1560,11 +1034,7 @@ __global__ void k_depth_minmax(const float* __restrict__ d, long long n, uint32_
         lo = __builtin_fminf(lo, d[i]);
         hi = __builtin_fmaxf(hi, d[i]);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        lo = __builtin_fminf(lo, __shfl_xor(lo, o));
-        hi = __builtin_fmaxf(hi, __shfl_xor(hi, o));
-    }
+    p3d_wave_minmax(true, lo, hi);
     if ((threadIdx.x & 63) == 0) {
         atomicMin(g, p3d_f2ord(lo));
         atomicMax(g + 1, p3d_f2ord(hi));
@@ -1582,38 +1052,27 @@ __global__ void k_composite(const float* __restrict__ colors, const float* __res
     const float* col = colors + r * S * K;
     const float* sg = sigma + r * S;
     const float* t = depths + r * S;
-    MarchState st;
-    st.Td = 1.0; st.W = 0.0f; st.D = 0.0f; st.prev_t = t[0]; st.prev_sigma = sg[0];
+    MarchState st = p3d_march_start(t[0], sg[0]);
     float C[8];  // up to 8 channels per thread (K <= 8*KS)
 #pragma unroll
     for (int q = 0; q < 8; ++q) C[q] = 0.0f;
     for (int i = 1; i < S; ++i) {
-        float tm;
-        float w = p3d_march_weight(st, t[i], sg[i], tm);
-        if (out_w && c0 == 0) out_w[r * (S - 1) + i - 1] = w;
+        const P3dInterval iv = p3d_march_interval(st, t[i], sg[i]);
+        if (out_w && c0 == 0) out_w[r * (S - 1) + i - 1] = iv.w;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             int k = c0 + q * KS;
-            if (k < K) C[q] = p3d_fma(w, (col[(i - 1) * K + k] + col[i * K + k]) * 0.5f, C[q]);
+            if (k < K) C[q] = p3d_composite_channel(iv.w, col[(i - 1) * K + k], col[i * K + k], C[q]);
         }
-        st.W = st.W + w;
-        st.D = p3d_fma(w, tm, st.D);
+        p3d_march_accumulate(st, iv);
         st.prev_t = t[i]; st.prev_sigma = sg[i];
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         int k = c0 + q * KS;
-        if (k < K) {
-            float v = C[q];
-            if (white_back) v = (v + 1.0f) - st.W;
-            out_rgb[r * K + k] = v * 2.0f - 1.0f;
-        }
+        if (k < K) out_rgb[r * K + k] = p3d_white_back_rescale(C[q], white_back, st.W);
     }
-    if (c0 == 0) {
-        float d = st.D / st.W;
-        if (d != d) d = __builtin_inff();
-        out_depth[r] = d;
-    }
+    if (c0 == 0) out_depth[r] = p3d_ray_depth(st);
 }
 
 // sample_importance + sample_pdf, one thread per ray, scratch in registers/local memory — renderer.py:328-387
@@ -1628,19 +1087,14 @@ __global__ void k_importance(const float* __restrict__ depths, const float* __re
     float cdf[P3D_MAX_S];
     double sum = 0.0;
     for (int jj = 0; jj < Ns; ++jj) {
-        float m1 = __builtin_fmaxf(w[jj], w[jj + 1]), m2 = __builtin_fmaxf(w[jj + 1], w[jj + 2]);
-        float v = ((m1 + m2) * 0.5f + 0.01f) + 1e-5f;
+        float v = p3d_pdf_bin(w[jj], w[jj + 1], w[jj + 2]);
         sum += (double)v;
         cdf[jj + 1] = v;
     }
     float fsum = (float)sum;
     double acc = 0.0;
     cdf[0] = 0.0f;
-    for (int jj = 0; jj < Ns; ++jj) {
-        float pdf = cdf[jj + 1] / fsum;
-        acc += (double)pdf;
-        cdf[jj + 1] = (float)acc;
-    }
+    for (int jj = 0; jj < Ns; ++jj) cdf[jj + 1] = p3d_cdf_step(acc, cdf[jj + 1], fsum);
     for (int i = 0; i < Sf; ++i) {
         float ui = u[r * Sf + i];
         int lo = 0, hi = Ns + 1;

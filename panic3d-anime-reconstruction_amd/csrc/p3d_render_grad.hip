@@ -4,7 +4,7 @@
 //   k_g_range       per-call / per-view min and max of the merged depths (the depth clamp of ray_marcher.py:49-50);
 //   k_g_decode      one lane per merged sample: exact-contract re-decode -> the density the forward composited, whether a mask
 //                   overwrote it, and s_i = <g_feat, c_i> + <g_xyz, p_i> (the only way a sample's colour enters the weight gradient);
-//   k_g_ray         one lane per ray: the forward's weights again (binary64 transmittance, as the forward), then the alpha recursion
+//   k_g_ray         one lane per ray: the forward's weights again (p3d_march_interval, the forward's own), then the alpha recursion
 //                   back to front -> per sample the density gradient (zero where masked) and the colour coefficient w_{i-1} + w_i;
 //   k_g_mlp         one lane per sample, one wave per workgroup, 64 samples per step: re-decode, MLP backward, the decoder
 //                   gradient as a per-workgroup partial slab (fixed order: reproducible), the plane gradient as 256-byte
@@ -16,6 +16,7 @@
 // (order-mapped u32 min / max: the call, then one pair per view), then four f32 arrays and one byte array [S][N*R] (sample-major:
 // consecutive lanes are consecutive rays), then the slabs.
 #include "p3d_decode_grad.hpp"
+#include "p3d_ray_phases.hpp"
 #include "../../include/p3d_render_grad.h"
 
 #define G_WG 64                      // one wave per workgroup
@@ -368,28 +369,22 @@ __global__ __launch_bounds__(256) void k_g_ray(GRayArgs p) {
     const float wb = (p.o.flags & P3D_FLAG_WHITE_BACK) ? 1.0f : 0.0f;
     const float gconst = gW - 2.0f * wb * gsum;  // d/dw_j of  2 (sum w cmid + b (1 - W)) - 1  and of  W, the part common to all j
     // forward sweep: the forward's weights (ray_marcher.py:25-46, numerics as p3d_numerics.h "compositing")
-    double Td = 1.0;
-    float Wsum = 0.0f, Dsum = 0.0f;
-    float t0 = t[0], sg0 = p.SG[r], s0 = p.GS[r];
+    MarchState st = p3d_march_start(t[0], p.SG[r]);
+    float s0 = p.GS[r];
     for (int j = 0; j < S - 1; ++j) {
         const int64_t g1 = (int64_t)(j + 1) * NR + r;
         const float t1 = t[j + 1], sg1 = p.SG[g1], s1 = p.GS[g1];
-        const float dl = t1 - t0, sm = (sg0 + sg1) * 0.5f, tm = (t0 + t1) * 0.5f;
-        const float rho = p3d_softplus(sm - 1.0f);
-        const float alpha = 1.0f - p3d_exp(-(rho * dl));
-        const float T = (float)Td;
-        const float w = alpha * T;
-        Td = Td * (double)((1.0f - alpha) + 1e-10f);
-        Wsum = Wsum + w;
-        Dsum = p3d_fma(w, tm, Dsum);
+        const P3dInterval iv = p3d_march_interval(st, t1, sg1);
+        p3d_march_accumulate(st, iv);
         const int64_t g0 = (int64_t)j * NR + r;
-        p.A[g0] = alpha;
-        p.TT[g0] = T;
+        p.A[g0] = iv.alpha;
+        p.TT[g0] = iv.T;
         p.GS[g0] = (s0 + s1) + gconst;  // 2 <g_feat, cmid_j> + 2 <g_xyz, pmid_j> + g_W - 2 b (sum g_feat + sum g_xyz)
-        t0 = t1;
-        sg0 = sg1;
+        st.prev_t = t1;
+        st.prev_sigma = sg1;
         s0 = s1;
     }
+    const float Wsum = st.W, Dsum = st.D;
     // depth = clamp(nan_to_num(D / W, inf), tmin, tmax): its gradient passes only where D / W is finite and inside the range
     const uint32_t* mm = (p.o.flags & P3D_FLAG_PER_VIEW_CLAMP) ? p.mm + 2 + 2 * (r / p.R) : p.mm;
     const float tmin = p3d_ord2f(mm[0]), tmax = p3d_ord2f(mm[1]);

@@ -5,7 +5,8 @@
 
 Compiles each csrc/*.hip for gfx950 with the product's flags plus `-Rpass-analysis=kernel-resource-usage` (no GPU needed) and
 prints one row per kernel: SGPRs, VGPRs, AGPRs, scratch bytes per lane, waves per SIMD, SGPR / VGPR spills, static LDS.
-`--keep DIR` also leaves the ISA (`*.s`) of every source there, for reading the loops.
+`--keep DIR` also leaves the ISA (`*.s`) of every source there, for reading the loops, and appends the instruction count of every
+kernel in it (comment, directive and label lines stripped).
 """
 import argparse
 import os
@@ -24,6 +25,22 @@ B = P._build
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     return [re.sub(r"\(.*", "", x).replace("void ", "") for x in out[:len(names)]]
+
+
+def instruction_counts(path):
+    """{demangled kernel: instructions} of one kept gfx950 `.s`."""
+    out, cur = {}, None
+    for line in open(path, errors="replace"):
+        t = line.strip()
+        m = re.match(r"^(_Z\w+|k_\w+):", t)
+        if m:
+            cur = m.group(1)
+            out[cur] = 0
+        elif t.startswith(".Lfunc_end"):
+            cur = None
+        elif cur and t and not t.startswith((";", ".", "//")) and not re.match(r"^[.\w$]+:", t):
+            out[cur] += 1
+    return {d: out[n] for n, d in zip(out, demangle(list(out))) if out[n] > 0}
 
 
 def main():
@@ -55,6 +72,12 @@ def main():
             lines.append("%-64s %5d %5d %5d %8d %4d %7d %7d %7d" % (
                 nm[:64], g("TotalSGPRs"), g("VGPRs"), g("AGPRs"), g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"),
                 g("SGPRs Spill"), g("VGPRs Spill"), g(r"LDS Size \[bytes/block\]")))
+    if a.keep:
+        lines += ["", "# instructions per kernel in the kept ISA (comment, directive and label lines stripped)"]
+        for s in a.sources:
+            lines.append("# " + s)
+            isa = os.path.join(tmp, os.path.splitext(s)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s")
+            lines += ["%-64s %7d" % (k[:64], v) for k, v in instruction_counts(isa).items()]
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if a.out:
