@@ -39,6 +39,13 @@ class PasteArgs(C.Structure):
                [(n, C.c_float) for n in ("thresh_weight", "thresh_edges", "thresh_occ", "thresh_dxyz", "box_warp")]
 
 
+class PasteGradArgs(C.Structure):
+    """p3d_paste_grad_args (include/p3d_paste_grad.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("g_out", "g_paste", "mask", "xyz", "front", "g_image", "g_xyz", "g_front", "workspace")] + \
+               [("workspace_bytes", C.c_size_t)] + \
+               [(n, C.c_int32) for n in ("N", "r", "S", "front_shared", "normalize_images", "grad_sample")] + [("box_warp", C.c_float)]
+
+
 class ConvArgs(C.Structure):
     """p3d_conv_args"""
     _fields_ = [(n, C.c_void_p) for n in ("x", "w", "w_f16", "styles", "demod_coefs", "noise", "bias", "fir", "y", "workspace",
@@ -124,6 +131,11 @@ SYN_GRAD_SIGNATURES = {
     "p3d_conv_wgrad_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "p3d_torgb_combine_backward_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_paste_grad.h declares (the front-view paste's backward)
+PASTE_GRAD_SIGNATURES = {
+    "p3d_paste_front_backward_workspace_bytes": (_Z, [_I, _I]),
+    "p3d_paste_front_backward_f32": (_I, [C.POINTER(PasteGradArgs), _P]),
+}
 P3D_GRAD_STATS_BYTES = 256  # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
 
 _LIB = None
@@ -143,7 +155,8 @@ def lib():
                 print(f"panic3d_amd: {SO} does not match csrc/ (source hash): rebuilding", file=sys.stderr)
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
+                + list(PASTE_GRAD_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

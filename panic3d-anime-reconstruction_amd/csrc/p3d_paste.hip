@@ -20,25 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/panic3d_hip.h"
-
-#define DEV __device__ __forceinline__
-
-struct UpIdx { int i0, i1; float l; };
-DEV UpIdx up_index(int i, float scale, int r) {
-    float src = ((float)i + 0.5f) * scale - 0.5f;
-    src = src < 0.0f ? 0.0f : src;
-    UpIdx u;
-    u.i0 = (int)src;  // src >= 0: truncation = floor
-    u.i0 = u.i0 < r - 1 ? u.i0 : r - 1;
-    u.i1 = u.i0 + 1 < r ? u.i0 + 1 : r - 1;
-    u.l = src - (float)u.i0;
-    return u;
-}
-DEV float bilerp(const float* m, int r, const UpIdx& y, const UpIdx& x) {
-    const float a00 = m[y.i0 * r + x.i0], a01 = m[y.i0 * r + x.i1], a10 = m[y.i1 * r + x.i0], a11 = m[y.i1 * r + x.i1];
-    const float w0 = 1.0f - x.l, h0 = 1.0f - y.l;
-    return h0 * (w0 * a00 + x.l * a01) + y.l * (w0 * a10 + x.l * a11);
-}
+#include "p3d_paste_common.hpp"
 
 __global__ __launch_bounds__(256) void k_paste_front(p3d_paste_args a) {
     const int S = a.S, r = a.r;
@@ -114,15 +96,9 @@ __global__ __launch_bounds__(256) void k_paste_front(p3d_paste_args a) {
     const float* front = a.front + (size_t)(a.front_shared ? 0 : n) * 3 * S * S;
     float paste[3];
     {
-        const float v0 = 1.0f - (upy + a.box_warp * 0.5f) / a.box_warp, v1 = 1.0f - (upx + a.box_warp * 0.5f) / a.box_warp;
-        const float gx = v0 * 2.0f - 1.0f, gy = v1 * 2.0f - 1.0f;  // grid x <- vij[0], grid y <- vij[1]
-        float ix = ((gx + 1.0f) * (float)S - 1.0f) * 0.5f, iy = ((gy + 1.0f) * (float)S - 1.0f) * 0.5f;
-        ix = fminf(fmaxf(ix, 0.0f), (float)(S - 1));
-        iy = fminf(fmaxf(iy, 0.0f), (float)(S - 1));
-        const float fx0 = floorf(ix), fy0 = floorf(iy);
-        const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
-        const float tx = ix - fx0, ty = iy - fy0;
-        const float wnw = (1.0f - tx) * (1.0f - ty), wne = tx * (1.0f - ty), wsw = (1.0f - tx) * ty, wse = tx * ty;
+        const FrontTaps t = front_taps(upx, upy, a.box_warp, S);
+        const int x0 = t.x0, y0 = t.y0, x1 = x0 + 1, y1 = y0 + 1;
+        const float wnw = t.wnw, wne = t.wne, wsw = t.wsw, wse = t.wse;
         const bool bx = x1 < S, by = y1 < S;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {

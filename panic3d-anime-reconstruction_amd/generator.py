@@ -8,8 +8,10 @@ The super-resolution is inference-only by default (`image` carries no gradient);
 backward.  With grad enabled, `image_raw`, `image_depth`,
 `image_weights` and `image_xyz` carry gradients through the renderer's HIP backward to the decoder parameters and the planes
 (renderer.py), and from the planes through the synthesis network's HIP backward (stylegan2.SynthesisNetwork) to
-`ws`, the backbone's synthesis parameters, latent injections and conditioning tensors that require grad.  The mapping network
-stays inference-only (`ws` is the leaf), and so does the staged density-noise path.  Not mirrored: `sample` (broken in the reference, triplane.py:254-271).  The `paste_front`
+`ws`, the backbone's synthesis parameters, latent injections and conditioning tensors that require grad, and from `ws` through the
+mapping network (torch autograd over its fully-connected layers, the lrelu ones on the HIP bias_act backward) to `z`,
+`cond['resnet_feats']` and `backbone.mapping.*`; `update_emas` moves `w_avg` as the reference does.  The front-view paste has a HIP
+backward behind set_paste_grad() (paste.py).  The staged density-noise path stays inference-only.  Not mirrored: `sample` (broken in the reference, triplane.py:254-271).  The `paste_front`
 post-process (triplane.py:555-691) lives in paste.py.
 """
 import os
@@ -175,22 +177,31 @@ class TriPlaneGenerator(torch.nn.Module):
         if rk.get("c_gen_conditioning_force_ffhq", False):
             raise NotImplementedError("c_gen_conditioning_force_ffhq (fine-tuning hack, triplane.py:97-121)")
         return self.backbone.mapping(z, c * rk.get("c_scale", 0), cond, truncation_psi=truncation_psi,
-                                     truncation_cutoff=truncation_cutoff)
+                                     truncation_cutoff=truncation_cutoff, update_emas=update_emas)
 
     def mapping_zplus(self, zs, c, cond, truncation_psi=1, truncation_cutoff=None, update_emas=False):
         """One z per w slot (triplane.py:123-143): map every z, keep slot i of the i-th z's broadcast ws."""
         bs, n, dim = zs.shape
         if zs.stride(1) == 0:  # f() expands ONE z to all w slots (triplane.py:356): every slot maps the same z -> map it once
-            return self.mapping(zs[:, 0], c, cond, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
+            # (under autograd too: slot i of the one broadcast ws is slot i of the i-th copy's, and expand's backward sums the slots onto z)
+            return self.mapping(zs[:, 0], c, cond, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)
         c_new = c[:, None, :].repeat(1, n, 1).reshape(bs * n, -1)
         cond_new = cond
         if "resnet_feats" in cond:
             cond_new = {**cond, "resnet_feats": cond["resnet_feats"][:, None, :].repeat(1, n, 1).reshape(bs * n, -1)}
         ans = self.mapping(zs.reshape(bs * n, dim), c_new, cond_new, truncation_psi=truncation_psi,
-                           truncation_cutoff=truncation_cutoff)
+                           truncation_cutoff=truncation_cutoff, update_emas=update_emas)
         ans = ans.view(bs, n, n, -1)
         idx = torch.arange(n, device=ans.device)
         return ans[:, idx, idx]
+
+    def _mapping_records_grad(self, cond):
+        """A mapping call now would record autograd for something other than z: grad mode on and a mapping parameter or the resnet
+        features requiring grad."""
+        if not torch.is_grad_enabled():
+            return False
+        feats = cond.get("resnet_feats") if self.backbone.mapping.resnet_cond > 0 else None
+        return (feats is not None and feats.requires_grad) or any(p.requires_grad for p in self.backbone.mapping.parameters())
 
     # ---- planes -------------------------------------------------------------------------------------------------
     def _planes(self, ws, cond, latent_injection=None, stop_level=None, **synthesis_kwargs):
@@ -480,8 +491,8 @@ class TriPlaneGenerator(torch.nn.Module):
 
     def forward(self, z, c, cond, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None,
                 update_emas=False, cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
-        ws = self.mapping(z, c, cond, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
-        return self.synthesis(ws, c, cond, neural_rendering_resolution=neural_rendering_resolution,
+        ws = self.mapping(z, c, cond, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)
+        return self.synthesis(ws, c, cond, neural_rendering_resolution=neural_rendering_resolution, update_emas=update_emas,
                               cache_backbone=cache_backbone, use_cached_backbone=use_cached_backbone, **synthesis_kwargs)
 
     # ---- the dict-in / dict-out API of PAniC-3D (triplane.py:313-508) -----------------------------------------
@@ -504,7 +515,10 @@ class TriPlaneGenerator(torch.nn.Module):
                 # parameter versions, the conditioning tensors it uses (object + version, strong references) — one entry deep.
                 rc = self.backbone.mapping.resnet_cond
                 pose_free = bool(self.rendering_kwargs.get("c_gen_conditioning_zero", False)) or self.c_dim == 0
-                if pose_free and latent_injection is None and memo.enabled():
+                # (not under autograd with a mapping input that requires grad: that ws carries a grad_fn of its own call; not with
+                # update_emas: the call moves w_avg)
+                if pose_free and latent_injection is None and memo.enabled() and not x.get("update_emas") \
+                        and not self._mapping_records_grad(x["cond"]):
                     ct = [x["cond"]["resnet_feats"]] if rc > 0 else []
                     # (the mapping network's tensors through its modules' own dicts: parameters() / buffers() walk the module tree
                     # through generators, ~25 us at the head of every call)
@@ -574,7 +588,7 @@ class TriPlaneGenerator(torch.nn.Module):
                                        "generator without pose conditioning (c_gen_conditioning_zero, PAniC-3D's default)")
                 cpm = cpm[:1]
             x["ws"] = self.mapping_zplus(x["zs"], cpm, x["cond"], truncation_psi=truncation_psi,
-                                         truncation_cutoff=truncation_cutoff)
+                                         truncation_cutoff=truncation_cutoff, update_emas=bool(x.get("update_emas", False)))
             if ws_key is not None:
                 self.__dict__["_ws_memo"] = (ws_key[0], ws_key[1], x["z"], x["ws"], (x["z"]._version, x["ws"]._version))
         _ws = x["ws"]
@@ -587,6 +601,7 @@ class TriPlaneGenerator(torch.nn.Module):
                                triplane_crop=x.get("triplane_crop"), cull_clouds=x.get("cull_clouds"),
                                binarize_clouds=x.get("binarize_clouds"), force_rays=force_rays, stop_level=stop_level,
                                normalize_images=normalize_images, neural_rendering_resolution=res,
+                               update_emas=bool(x.get("update_emas", False)),
                                # extensions of the dict API (absent keys = the reference's behaviour): reuse the planes of
                                # the previous call for further views of the same subject, deterministic backbone noise
                                cache_backbone=bool(x.get("cache_backbone", False)),
@@ -596,9 +611,10 @@ class TriPlaneGenerator(torch.nn.Module):
         ret["normalize_images"] = normalize_images
         x.update(ret)
         if x.get("paste_params") is not None:  # front-view paste post-process (triplane.py:497-502)
-            if ret["image"].requires_grad:
-                raise NotImplementedError("the front-view paste has no backward: call G.f with paste_params under torch.no_grad(), or turn "
-                                          "the super-resolution's gradient off (set_superresolution_grad(False))")
+            if ret["image"].requires_grad and not self.__dict__.get("paste_grad"):
+                raise NotImplementedError("the front-view paste's backward is off: call G.set_paste_grad(True), call G.f with paste_params "
+                                          "under torch.no_grad(), or turn the super-resolution's gradient off "
+                                          "(set_superresolution_grad(False))")
             from .paste import paste_front
             ret["image_prepaste"] = ret["image"]
             ret["paste"] = paste_front(self, x, ret, **x["paste_params"])
@@ -692,6 +708,16 @@ class TriPlaneGenerator(torch.nn.Module):
         default): the super-resolution runs under no_grad whatever the caller's mode.  Drops the captured views."""
         self.__dict__["_view_graphs"] = None
         self.superresolution.__dict__["record_grad"] = bool(state)
+        return bool(state)
+
+    def set_paste_grad(self, state=True):
+        """Opt-in: let the front-view paste (G.f with paste_params) record its HIP backward (paste.py).  With the switch
+        on and autograd recording, the loss gradient reaches the pre-paste image through the lerp and — with paste_params' grad_sample —
+        `image_xyz` (and from there the renderer's backward) and an illustration that requires grad, through the sampling; the outputs
+        are the no-grad call's bits.  Off (the default): a pasted call whose image records a gradient raises, and every other pasted call
+        runs under no_grad.  Drops the captured views."""
+        self.__dict__["_view_graphs"] = None
+        self.__dict__["paste_grad"] = bool(state)
         return bool(state)
 
     def set_sr_mma_f16(self, state=True):

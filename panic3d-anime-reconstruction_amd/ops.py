@@ -537,6 +537,82 @@ def paste_front(weights, xyz, occ, rays_o, rays_d, front, image, thresh_weight, 
     return out
 
 
+def paste_front_backward(g_out, g_paste, mask, xyz, front, box_warp, normalize_images, grad_sample, want_image=True, want_xyz=False,
+                         want_front=False):
+    """p3d_paste_front_backward_f32 (include/p3d_paste_grad.h): the cotangents of the pasted image and of the returned paste (either
+    may be None) -> (g_image [N,3,S,S], g_xyz [N,3,r,r], g_front like front), each None unless asked for.  g_xyz / g_front exist
+    only with grad_sample (otherwise the paste is a constant)."""
+    mask, xyz, front = _chk(mask, "mask"), _chk(xyz, "xyz"), _chk(front, "front")
+    g_out = _chk(g_out, "g_out") if g_out is not None else None
+    g_paste = _chk(g_paste, "g_paste") if g_paste is not None else None
+    N, _, r, r2 = xyz.shape
+    S = mask.shape[-1]
+    if (r != r2 or xyz.shape[1] != 3 or tuple(mask.shape) != (N, 1, S, S) or front.shape[0] not in (1, N) or tuple(front.shape[1:]) != (3, S, S)
+            or any(g is not None and tuple(g.shape) != (N, 3, S, S) for g in (g_out, g_paste))):
+        raise RuntimeError("paste_front_backward: g_out/g_paste [N,3,S,S], mask [N,1,S,S], xyz [N,3,r,r], front [N|1,3,S,S]")
+    if g_out is None and g_paste is None:
+        raise RuntimeError("paste_front_backward: no cotangent")
+    if (want_xyz or want_front) and not grad_sample:
+        raise RuntimeError("paste_front_backward: g_xyz / g_front exist only with grad_sample")
+    dev = mask.device
+    g_image = torch.empty((N, 3, S, S), dtype=torch.float32, device=dev) if want_image else None
+    g_xyz = torch.empty((N, 3, r, r), dtype=torch.float32, device=dev) if want_xyz else None
+    g_front = torch.empty(tuple(front.shape), dtype=torch.float32, device=dev) if want_front else None
+    if g_image is None and g_xyz is None and g_front is None:
+        return None, None, None
+    L = _lib.lib()
+    ws = _sg_workspace(dev, L.p3d_paste_front_backward_workspace_bytes(N, S)) if want_xyz else None
+    a = _lib.PasteGradArgs(_p(g_out).value, _p(g_paste).value, _p(mask).value, _p(xyz).value, _p(front).value, _p(g_image).value,
+                           _p(g_xyz).value, _p(g_front).value, _p(ws).value, ws.numel() if ws is not None else 0,
+                           N, r, S, int(front.shape[0] == 1 and N > 1), int(bool(normalize_images)), int(bool(grad_sample)), np.float32(box_warp))
+    with _on(dev):
+        rc = L.p3d_paste_front_backward_f32(C.byref(a), _stream())
+    _lib.check(rc, "p3d_paste_front_backward_f32")
+    return g_image, g_xyz, g_front
+
+
+class _PasteFrontFn(torch.autograd.Function):
+    """paste_front's one launch forward (the no-grad call's bits) with the HIP backward of include/p3d_paste_grad.h.  Differentiable
+    inputs: image, and with grad_sample xyz and the illustration; the masks are constants, as in the reference (they are computed
+    under no_grad there).  Returns (image, paste) and hands the masks out through `res`."""
+
+    @staticmethod
+    def forward(ctx, image, xyz, front, call, res):
+        out = paste_front(call["weights"], xyz, call["occ"], call["rays_o"], call["rays_d"], front, image, *call["thresholds"],
+                          call["box_warp"], call["normalize_images"])
+        res.update(out)
+        ctx.save_for_backward(out["mask"], xyz, front)
+        ctx.call = call
+        ctx.set_materialize_grads(False)  # an output nobody differentiates arrives as None, not as a tensor of zeros
+        return out["image"], out["paste"]
+
+    @staticmethod
+    def backward(ctx, g_image, g_paste):
+        mask, xyz, front = ctx.saved_tensors
+        call = ctx.call
+        gs = bool(call["grad_sample"])
+        if not gs:
+            g_paste = None  # the paste is a constant: its cotangent reaches nothing
+        if g_image is None and g_paste is None:
+            return None, None, None, None, None
+        gi, gx, gf = paste_front_backward(g_image, g_paste, mask, xyz, front, call["box_warp"], call["normalize_images"], gs,
+                                          want_image=ctx.needs_input_grad[0] and g_image is not None,
+                                          want_xyz=gs and ctx.needs_input_grad[1], want_front=gs and ctx.needs_input_grad[2])
+        return gi, gx, gf, None, None
+
+
+def paste_front_grad(weights, xyz, occ, rays_o, rays_d, front, image, thresh_weight, thresh_edges, thresh_occ, thresh_dxyz, box_warp,
+                     normalize_images, grad_sample=False):
+    """ops.paste_front under autograd: the same launch and the same dict; `image` (and `paste`, with grad_sample) carry the HIP backward."""
+    res = {}
+    call = dict(weights=weights.detach(), occ=occ.detach(), rays_o=rays_o.detach(), rays_d=rays_d.detach(),
+                thresholds=(thresh_weight, thresh_edges, thresh_occ, thresh_dxyz), box_warp=box_warp, normalize_images=normalize_images,
+                grad_sample=grad_sample)
+    img, paste = _PasteFrontFn.apply(image, xyz if grad_sample else xyz.detach(), front if grad_sample else front.detach(), call, res)
+    res["image"], res["paste"] = img, paste if grad_sample else paste.detach()
+    return res
+
+
 def depth_minmax(depths):
     """torch.min(depths), torch.max(depths) of ray_marcher.py:50 as one op -> float32 tensor [2] on the device."""
     depths = _chk(depths, "depths")

@@ -4,6 +4,8 @@ illustration sampled at the rendered xyz.  Two launches: ONE extra pass through 
 test (rays from the rendered surface points towards the front plane, triplane.py:565-578), then ONE fused kernel
 (`ops.paste_front` -> p3d_paste_front_f32, csrc/p3d_paste.hip) for the four masks, the sampling of the illustration and the
 lerp — the reference runs three bilinear resizes, a Sobel, a nearest resize, a grid_sample and a lerp over 512^2 x N pixels.
+With G.set_paste_grad(True) a call under autograd records the paste's HIP backward (include/p3d_paste_grad.h): the
+loss gradient reaches the pre-paste image through the lerp and, with `grad_sample`, `image_xyz` and the illustration through the sampling.
 
 kornia is not a dependency: the kernel restates kornia 0.6.5 `kornia.filters.sobel(x, normalized=True, eps=1e-6)` (3x3
 Sobel kernels divided by 8, replicate padding, sqrt(gx^2 + gy^2 + eps)) — "parity unpinned": kornia cannot be installed here
@@ -89,11 +91,20 @@ def paste_front(G, x, out, mode="default", thresh_weight=0.95, thresh_edges=0.02
         return paste_front_torch(G, x, out, mode=mode, thresh_weight=thresh_weight, thresh_edges=thresh_edges, thresh_occ=thresh_occ,
                                  offset_occ=offset_occ, thresh_dxyz=thresh_dxyz, front_weight_erosion=front_weight_erosion,
                                  grad_sample=grad_sample, force_image=force_image, **kwargs)
+    front = x["cond"]["image_ortho_front"]
+    args = (x["force_rays"]["ray_origins"], x["force_rays"]["ray_directions"], front, out["image"], thresh_weight, thresh_edges, thresh_occ,
+            thresh_dxyz, G.rendering_kwargs["box_warp"], x["normalize_images"])
     with torch.no_grad():
         occ = front_occlusion(G, x, out, offset=offset_occ)
-        res = ops.paste_front(out["image_weights"], out["image_xyz"], occ, x["force_rays"]["ray_origins"], x["force_rays"]["ray_directions"],
-                              x["cond"]["image_ortho_front"], out["image"], thresh_weight, thresh_edges, thresh_occ, thresh_dxyz,
-                              G.rendering_kwargs["box_warp"], x["normalize_images"])
+    records = G.__dict__.get("paste_grad") and torch.is_grad_enabled() and (
+        out["image"].requires_grad or (grad_sample and (out["image_xyz"].requires_grad or front.requires_grad)))
+    if records:
+        # G.set_paste_grad(True): the same launch with the HIP backward recorded (ops._PasteFrontFn, include/p3d_paste_grad.h) — the masks
+        # and the occlusion render stay under no_grad, as in the reference (triplane.py:621-665)
+        res = ops.paste_front_grad(out["image_weights"], out["image_xyz"], occ, *args, grad_sample=grad_sample)
+    else:
+        with torch.no_grad():
+            res = ops.paste_front(out["image_weights"], out["image_xyz"], occ, *args)
     return {"image": res["image"], "paste": res["paste"], "mask": res["mask"], "mask_weights": res["mask_weights"],
             "mask_edges": res["mask_edges"], "mask_occ": res["mask_occ"], "mask_dxyz": res["mask_dxyz"],
             "mask_frontweight": torch.ones_like(res["mask_dxyz"]), "frontweight": None}

@@ -4,7 +4,8 @@ Mirrors the module tree and parameter names of training/networks_stylegan2.py (F
 MappingNetwork :199-296, SynthesisLayer :299-360, ToRGBLayer :363-383, SynthesisBlock :388-487, SynthesisNetwork
 :492-725, Generator :729-757) so that `misc.copy_params_and_buffers(..., require_all=True)` / `load_state_dict` of a
 PAniC-3D checkpoint works unchanged.  fp32 only (the backbone runs with num_fp16_res=0: trainers/train_eclustrousC.py:253,553).
-The mapping network is inference-only; SynthesisNetwork.forward records a HIP backward when autograd records and ws, a parameter,
+The mapping network records torch autograd over its fully-connected layers, with the lrelu layers on the HIP bias_act forward /
+backward (FullyConnectedLayer); SynthesisNetwork.forward records a HIP backward when autograd records and ws, a parameter,
 a latent injection or a conditioning tensor requires grad.  All convolution-shaped work runs in libpanic3d_hip.so: each SynthesisLayer /
 ToRGBLayer is ONE fused call (modulation, conv on the matrix cores, demodulation, noise, bias, lrelu, gain, clamp);
 the tiny fully-connected layers (w -> styles, mapping) stay on torch matmul.
@@ -60,11 +61,51 @@ class FullyConnectedLayer(_CacheFree):
             self._scaled_wb, self._scaled_key = (w, b), key
         return self._scaled_wb
 
+    def _records_grad(self, x):
+        if not torch.is_grad_enabled():
+            return False
+        return x.requires_grad or self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad)
+
     def forward(self, x):
+        if self._records_grad(x):
+            # under autograd: the same two multiplications as live ops (the memoised detached copy stays as it is for no-grad calls),
+            # so the forward's bits are the no-grad call's; the affine layers of the synthesis / ToRGB layers and the decoder never
+            # get here under autograd from their networks (StylePlan.with_grad / renderer.decoder_params record their own copies)
+            w = self.weight.to(x.dtype) * self.weight_gain
+            b = self.bias
+            if b is not None:
+                b = b.to(x.dtype)
+                if self.bias_gain != 1:
+                    b = b * self.bias_gain
+            if self.activation == "linear":
+                return torch.addmm(b.unsqueeze(0), x, w.t()) if b is not None else x.matmul(w.t())
+            return _FcActFn.apply(x, w, b, self.activation)
         w, b = self._scaled(x.dtype)
         if self.activation == "linear" and b is not None:
             return torch.addmm(b.unsqueeze(0), x, w.t())
         return ops.bias_act(x.matmul(w.t()).contiguous(), b, act=self.activation)
+
+
+class _FcActFn(torch.autograd.Function):
+    """bias_act(x @ w^T, b) of a fully-connected layer with an activation: the no-grad call's launches forward; backward on
+    p3d_bias_act_backward_f32 with the mask taken from the OUTPUT (no pre-activation is kept), the [N,C] result seen as [N,C,1,1]."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act):
+        y = ops.bias_act(x.matmul(w.t()).contiguous(), b, act=act)
+        ctx.save_for_backward(x, w, y)
+        ctx.act, ctx.has_bias = act, b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, y = ctx.saved_tensors
+        idx, alpha, gain = ops._ACTS[ctx.act]
+        gz, gb, _ = ops.bias_act_backward(y, g.contiguous(), idx, alpha, gain, None)
+        gx = gz.matmul(w) if ctx.needs_input_grad[0] else None
+        gw = gz.t().matmul(x) if ctx.needs_input_grad[1] else None
+        gbias = gb.sum(dim=0) if ctx.has_bias and ctx.needs_input_grad[2] else None  # [N,C] sums over "pixels" -> column sums
+        return gx, gw, gbias, None
 
 
 class MappingNetwork(torch.nn.Module):
@@ -90,7 +131,6 @@ class MappingNetwork(torch.nn.Module):
             self.register_buffer("w_avg", torch.zeros([w_dim]))
 
     def forward(self, z, c, cond, truncation_psi=1, truncation_cutoff=None, update_emas=False):
-        assert not update_emas, "inference only"
         x = None
         if self.z_dim > 0:
             x = normalize_2nd_moment(z.to(torch.float32))
@@ -101,6 +141,8 @@ class MappingNetwork(torch.nn.Module):
             x = torch.cat([x, y], dim=1) if x is not None else y
         for i in range(self.num_layers):
             x = getattr(self, f"fc{i}")(x)
+        if update_emas and self.w_avg_beta is not None:  # networks_stylegan2.py:273-276
+            self.w_avg.copy_(x.detach().mean(dim=0).lerp(self.w_avg, self.w_avg_beta))
         if self.num_ws is not None:
             x = x.unsqueeze(1).repeat([1, self.num_ws, 1])
         if truncation_psi != 1:
@@ -891,5 +933,5 @@ class Generator(torch.nn.Module):
                                       **mapping_kwargs)
 
     def forward(self, z, c, cond, truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs):
-        ws = self.mapping(z, c, cond, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
+        ws = self.mapping(z, c, cond, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)
         return self.synthesis(ws, cond, **synthesis_kwargs)
