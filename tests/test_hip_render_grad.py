@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import p3d_testing as T
+from render_grad_ref import restate64
 
 pytestmark = pytest.mark.gpu
 
@@ -107,59 +108,6 @@ def test_run_model_grad_vs_reference(P):
         errs[key] = rel_l2(x, g[key])
     print("run_model", {k: f"{v:.2e}" for k, v in errs.items()})
     assert max(errs.values()) <= REL_TOL, errs
-
-
-# ---- fp64 restatement at the HIP forward's merged depths -----------------------------------------------------------------------
-def restate64(planes, mlp, rays_o, rays_d, depths, sig_dump, opts, ro, cot, per_view, fsig):
-    """ray_marcher.py + renderer.py + triplane.py as float64 torch ops at the given merged depths; mask decisions taken from the
-    forward's own sigma dump (a cull decision must not flip between binary32 and binary64).  Returns the loss's gradients."""
-    N, R, _ = rays_o.shape
-    S = depths.shape[-1]
-    pl = planes.double().detach().requires_grad_(True)
-    w0, b0, w1, b1 = (t.double().detach().requires_grad_(True) for t in mlp)
-    t = depths.double().reshape(N, R, S, 1)
-    pts = rays_o.double().unsqueeze(-2) + t * rays_d.double().unsqueeze(-2)  # [N,R,S,3]
-    q = pts.reshape(N, -1, 3) * (2.0 / ro["box_warp"])
-    axes = [(0, 1), (0, 2), (1, 2) if ro["use_triplane"] else (2, 0)]
-    Np = pl.shape[0]
-    feats = 0
-    for p, (a, b) in enumerate(axes):
-        grid = torch.stack([q[..., a], q[..., b]], -1).reshape(N, 1, -1, 2)
-        src = pl[:, p].expand(N, -1, -1, -1) if Np == 1 and N > 1 else pl[:, p]
-        feats = feats + torch.nn.functional.grid_sample(src, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
-    X = (feats / 3).reshape(N, 32, -1).permute(0, 2, 1)
-    h = torch.nn.functional.softplus(X @ w0.t() + b0)
-    o = h @ w1.t() + b1
-    sigma = o[..., :1].reshape(N, R, S, 1)
-    rgb = torch.sigmoid(o[..., 1:]) if fsig else torch.sigmoid(o[..., 1:]) * 1.002 - 0.001
-    rgb = rgb.reshape(N, R, S, 32)
-    sd = sig_dump.reshape(N, R, S, 1).double()
-    masked = (sd == -1000.0) | (sd == 1000.0)
-    sigma = torch.where(masked, sd, sigma)
-    colors = torch.cat([rgb, pts], -1)
-    deltas = t[:, :, 1:] - t[:, :, :-1]
-    cm = (colors[:, :, :-1] + colors[:, :, 1:]) / 2
-    dm = torch.nn.functional.softplus((sigma[:, :, :-1] + sigma[:, :, 1:]) / 2 - 1)
-    tm = (t[:, :, :-1] + t[:, :, 1:]) / 2
-    alpha = 1 - torch.exp(-dm * deltas)
-    T_ = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :, :1]), 1 - alpha + 1e-10], -2), -2)[:, :, :-1]
-    w = alpha * T_
-    comp = (w * cm).sum(-2)
-    W = w.sum(2)
-    D = (w * tm).sum(-2) / W.clamp_min(1e-300)
-    D = torch.where(W > 0, D, torch.full_like(D, float("inf")))
-    if per_view:
-        lo = t.reshape(N, -1).min(1).values.view(N, 1, 1)
-        hi = t.reshape(N, -1).max(1).values.view(N, 1, 1)
-        D = torch.minimum(torch.maximum(D, lo), hi)
-    else:
-        D = torch.clamp(D, t.min().item(), t.max().item())
-    if ro.get("white_back", False):
-        comp = comp + 1 - W
-    comp = comp * 2 - 1
-    loss = (comp[..., :32] * cot[0]).sum() + (D * cot[1]).sum() + (W * cot[2]).sum() + (comp[..., 32:] * cot[3]).sum()
-    loss.backward()
-    return pl.grad, [x.grad for x in (w0, b0, w1, b1)]
 
 
 BENCH_MODES = [  # (Sc, Sf, exact, views, ro overrides)
