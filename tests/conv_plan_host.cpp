@@ -3,6 +3,9 @@
 //   s N I O H W up                                  sweep every operand mode, input / output kind, act and forcing switch of
 //                                                   this shape and check that each plan's carve-up fits the workspace query
 //   p N I O H W ks up mma x_img y_img rgb act alpha  print the default-environment plan of one call: main ksplit reduce tail
+//   q N I O H W ks up mma x_img y_img rgb act alpha up4 up4_rpw up3_fused up5 fir_img2
+//                                                   print the plan of one call under those five switches (-1: not set):
+//                                                   main ksplit reduce tail fir_sums pre_image main_img (tests/test_modconv_cases_cpu.py)
 // Exit status 1 and a line on stderr for every plan that does not fit.
 #include <stdio.h>
 #include <string.h>
@@ -76,6 +79,17 @@ int main() {
             int N, I, O, H, W, up;
             if (scanf("%d %d %d %d %d %d", &N, &I, &O, &H, &W, &up) != 6) return 2;
             bad |= sweep(N, I, O, H, W, up);
+        } else if (!strcmp(kind, "q")) {
+            ConvCall c;
+            ConvSwitches s;
+            int x_img, y_img, rgb;
+            if (scanf("%d %d %d %d %d %d %d %d %d %d %d %d %f %d %d %d %d %d", &c.N, &c.I, &c.O, &c.H, &c.W, &c.ks, &c.up, &c.mma, &x_img, &y_img,
+                      &rgb, &c.act, &c.alpha, &s.up4, &s.up4_rpw, &s.up3_fused, &s.up5, &s.fir_img2) != 18)
+                return 2;
+            c.x_img = x_img; c.y_img = y_img; c.rgb = rgb;
+            const ConvPlan pl = p3d_conv_plan(c, s);
+            printf("q %s %d %s %s %d %d %d\n", kernel_name(pl.main), pl.ksplit, reduce_name(pl.reduce), tail_name(pl.tail), (int)pl.fir_sums,
+                   (int)pl.pre_image, (int)pl.main_img);
         } else {
             ConvCall c;
             int x_img, y_img, rgb;

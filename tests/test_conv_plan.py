@@ -41,6 +41,9 @@ def test_shape_queries_answer_the_recorded_values(L):
 # before it wrote and writes an image where its own conv1 takes one (maps >= 32^2), fp32 below; conv1 reads an image from 32^2 up and
 # writes y plus the next conv0's image; the super-resolution's conv1 layers take their ToRGB layer along.  Each call: two-term
 # operands, lrelu.  The table was checked once against a kernel trace of an eager backbone + super-resolution pass on the GPU.
+# What each of these plans COMPUTES is pinned elsewhere: tests/modconv_cases.py reaches every kernel, reduction and tail the plan can name
+# (tests/test_modconv_cases_cpu.py checks that against this header) and tests/test_hip_modconv_edges.py runs every case on the GPU
+# against the float64 reference and gate of tests/modconv_ref.py.
 def _calls():
     out = []
     for name, I, O, r, up in K.BACKBONE + K.SUPERRES:

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import p3d_testing as T
+from modconv_ref import torch_modconv_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -74,30 +75,6 @@ def test_fir_and_bias_act_vs_reference(hip):
     assert np.array_equal(hip.ops.bias_act(xb, bb, act="lrelu").cpu().numpy(), g["ba_lrelu"])  # same fp32 ops: exact
     assert np.array_equal(hip.ops.bias_act(xb, bb, act="linear", gain=2.0, clamp=1.5).cpu().numpy(), g["ba_lin_clamp"])
     assert np.array_equal(hip.ops.bias_act(xb.reshape(3, -1)[:, :7].contiguous(), bb, act="lrelu").cpu().numpy(), g["ba_fc"])
-
-
-def torch_modconv_ref(x, w, s, noise, up, demod, bias, f):
-    """Plain PyTorch fp32 (CPU) restatement of modulated_conv2d + bias/lrelu: per-sample weights, grouped conv."""
-    N, I, H, W = x.shape
-    O, _, k, _ = w.shape
-    ww = w.unsqueeze(0) * s.reshape(N, 1, I, 1, 1)
-    if demod:
-        ww = ww * (ww.square().sum(dim=[2, 3, 4], keepdim=True) + 1e-8).rsqrt()
-    ys = []
-    for n in range(N):
-        if up == 1:
-            y = F.conv2d(x[n:n + 1], ww[n], padding=k // 2)
-        else:
-            y = F.conv_transpose2d(x[n:n + 1], ww[n].transpose(0, 1), stride=2)
-            ff = (f * 4).flip([0, 1])[None, None].repeat(O, 1, 1, 1)
-            y = F.conv2d(F.pad(y, [1, 1, 1, 1]), ff, groups=O)
-        ys.append(y)
-    y = torch.cat(ys)
-    if noise is not None:
-        y = y + noise
-    if bias is not None:
-        y = y + bias.reshape(1, -1, 1, 1)
-    return y
 
 
 @pytest.mark.parametrize("I,O,H,up,ks", [(512, 512, 16, 1, 3), (512, 512, 8, 2, 3), (256, 128, 32, 2, 3), (128, 96, 64, 1, 1),
