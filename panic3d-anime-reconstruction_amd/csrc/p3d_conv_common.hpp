@@ -1,5 +1,8 @@
 // p3d_conv_common.hpp — what the translation units of the StyleGAN2 synthesis operators share: the launch parameters of the
-// convolution kernels, the two-term operand scaling, the XCD-aware workgroup order and the inline-asm LDS-DMA helpers.
+// convolution kernels, the two-term operand scaling, the XCD-aware workgroup order, the inline-asm LDS-DMA helpers and the steps
+// every convolution kernel takes the same way ("the shared steps" below: the K slice of a workgroup, accumulator zeroing and the
+// accumulator-to-channel map, the tap table of the transposed convolution, the patch / weight DMA plans of the
+// image-fed kernels, the raw four-phase store).  k_modconv_up4 (p3d_conv_up4.hip) includes this header only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,6 +131,119 @@ DEV void w3_dma16(uint32_t lds_addr, i32x4 rsrc, int voff) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory");
 }
 #define W3_VMWAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+
+// =====================================================================================================================
+// The shared steps of the convolution kernels: each is defined here ONCE (the 8 x 16 tile origin and the ordinary epilogue of
+// the register-staged kernels: p3d_conv_stage.hpp).  Address arithmetic and stores only — every DMA issue, barrier, counted
+// wait and sched_barrier stays in the kernel bodies, which hand-count their vmcnt.
+// =====================================================================================================================
+
+// The K slice of a workgroup: z = n * ksplit + kz (blockIdx.z, WgOrder::z or k_modconv_up5's own order) -> sample n and input
+// channels [ic_beg, ic_end) = nch 16-channel chunks (the DMA kernels: I % 16 == 0).  The host plan (p3d_conv_plan.hpp:
+// conv_ksplit / conv_ksplit_up3) chooses ksplit and nothing else — the slice width is THIS function's: ceil(I / ksplit) rounded
+// up to 32 channels, so that every slice starts on a whole chunk of every kernel (8 / 16 channels) and of the image weight layouts
+// ([chunk][...], indexed ic0 >> 4).  The rounding can leave the last slices short or empty (ic_beg >= I: nch = 0, every load out of
+// range): such a workgroup stores a zero partial sum, which the plan's reduction (it sums all ksplit slices) relies on.
+// (Z: blockIdx.z as the unsigned it is, or an int — the quotient of an unsigned division is known to be non-negative, which the
+// 64-bit output addressing of the kernels that pass blockIdx.z is compiled with)
+struct ConvSlice { int n, kz, ic_beg, ic_end, nch; };
+template <typename Z>
+DEV ConvSlice conv_slice(const ConvParams& p, Z z) {
+    ConvSlice s;
+    s.n = z / p.ksplit;
+    s.kz = z - s.n * p.ksplit;
+    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
+    s.ic_beg = s.kz * ic_per;
+    s.ic_end = (s.ic_beg + ic_per < p.I) ? s.ic_beg + ic_per : p.I;
+    s.nch = s.ic_end > s.ic_beg ? (s.ic_end - s.ic_beg) >> 4 : 0;
+    return s;
+}
+// ksplit > 1: a launch stores raw partial sums into slice kz of the partial buffer
+DEV float* conv_yout(const ConvParams& p, int kz) { return p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0); }
+
+// acc = 0 for the accumulator arrays the kernels hold ([tile] or [phase | channel tile][row])
+template <int M>
+DEV void conv_zero(f32x16 (&acc)[M]) {
+#pragma unroll
+    for (int t = 0; t < M; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+}
+template <int M, int N>
+DEV void conv_zero(f32x16 (&acc)[M][N]) {
+#pragma unroll
+    for (int a = 0; a < M; ++a)
+#pragma unroll
+        for (int b = 0; b < N; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+}
+// register r of a 32x32 accumulator on lane half `half` holds this output channel of the tile's 32
+DEV constexpr int conv_acc_ch(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// The nine products of the stride-2 transposed 3x3 convolution in the order every kernel issues them: product q adds tap TP[q] times
+// input BO[q] (0 = x[y][x], 1 = x[y][x-1], 2 = x[y-1][x], 3 = x[y-1][x-1]) into output phase PH[q] = 2 py + px
+struct UpTaps {
+    static constexpr int PH[9] = {0, 1, 2, 3, 0, 2, 0, 1, 0}, TP[9] = {0, 1, 3, 4, 2, 5, 6, 7, 8}, BO[9] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
+};
+
+// ---- the patch of an image-fed kernel: sub-image (hi|lo = which, k half = kh) of the activation image, one 16-byte item per pixel.
+// Byte offset of item `it` (row pitch `pitch`, origin one above / left of the tile origin) inside a chunk's [k half][H][W] pieces;
+// CONV_OOB (the DMA then writes zeros) for padding and for `item` false (past the sub-image)
+DEV int conv_patch_voff(const ConvParams& p, int it, bool item, int pitch, int gy0, int gx0, int kh) {
+    const int r = it / pitch, c = it - r * pitch;
+    const int iy = gy0 - 1 + r, ix = gx0 - 1 + c;
+    const bool ok = item && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+    return ok ? ((kh * p.H + iy) * p.W + ix) * 16 : CONV_OOB;
+}
+DEV const char* conv_img_base(const ConvParams& p, int HW, int n, int which) {
+    return (const char*)p.ximg + (which ? p.ximg_lo : 0) + (size_t)n * (p.I >> 3) * HW * 16;
+}
+// (The per-chunk buffer resources — base = the chunk's first channel, zero length past the slice — stay lambdas of the kernels: the
+// scalar code of the K loops follows the way each kernel writes that select, and one shared form changed three of the loops.)
+// ---- the weights of the transposed kernels: 1152 pieces q = (hi|lo, tap, k half, o of 32) per chunk = 18 DMA instructions, wave w
+// of NW issues instructions w, w + NW, ...: byte offset of this lane's piece of the wave's i-th instruction.  wlds
+// (P3D_WLAYOUT_UP): the weights arrive as the kernels' LDS image [chunk][O/32][hi|lo][tap][k half][32 o][8] (18 KB of consecutive
+// bytes per chunk and channel tile, a request = 1 KB of them); else 16-byte pieces gathered out of [hi|lo][O][9][I].  The o0 + o < O
+// guard of the gathered form is ALWAYS there: k_modconv_up4's plan has O % 32 == 0 and needs none, and pays one compare per piece
+// in its prologue for the single definition.
+// (LO = O * 9 * I * 2: bytes of the hi tensor, the lo parts follow it)
+template <int NW>
+DEV int up_weight_voff(const ConvParams& p, int LO, int wave, int lane, int i, int o0, bool wlds) {
+    const int q = (wave + NW * i) * 64 + lane, which = q / 576, rem = q - which * 576;
+    const int tap = rem >> 6, kh = (rem >> 5) & 1, o = rem & 31;
+    return q >= 1152 ? CONV_OOB : wlds ? q * 16 : (o0 + o < p.O) ? which * LO + (((o0 + o) * 9 + tap) * p.I + 8 * kh) * 2 : CONV_OOB;
+}
+// ---- raw store of the four output phases of an 8 x 32 tile of grid points (wave w = grid rows 2w, 2w + 1, lane j = column j) into
+// the (2H+1) x (2W+1) intermediate or slice kz of the split-K partials: a lane owns both column phases (ox = 2 gx, 2 gx + 1) of its
+// grid point: one 8-byte store per (row phase, channel), 32 lanes = 256 contiguous bytes; the last grid column (gx = W) has only
+// px = 0: a 4-byte store of its own
+DEV void up_store_phases(const ConvParams& p, const f32x16 (&acc)[4][2], const ConvSlice& s, int o0, int gy0, int gx0, int wave, int half, int j) {
+    float* yout = conv_yout(p, s.kz) + (size_t)s.n * p.O * p.OH * p.OW;
+    const int OHW = p.OH * p.OW;
+    auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, p.O * OHW * 4, CONV_RSRC_FLAGS);
+    const int gx = gx0 + j;
+    const bool edge_tile = gx0 + WX_TW > p.W;  // (uniform) this tile holds the column gx = W
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int gy = gy0 + 2 * wave + t;
+#pragma unroll
+        for (int py = 0; py < 2; ++py) {
+            const bool row_ok = gy <= p.H - py;
+            const int base = ((o0 + 4 * half) * OHW + (2 * gy + py) * p.OW + 2 * gx + p.tox) * 4;
+            const int off2 = (row_ok && gx < p.W && o0 + 4 * half < p.O) ? base : CONV_OOB;
+            const int off1 = (row_ok && gx == p.W && o0 + 4 * half < p.O) ? base : CONV_OOB;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int so = conv_acc_ch(r, 0) * OHW * 4;
+                const float v0 = acc[2 * py][t][r] * HX_SPLIT_UNSCALE, v1 = acc[2 * py + 1][t][r] * HX_SPLIT_UNSCALE;
+                typedef int i32x2 __attribute__((ext_vector_type(2)));
+                __builtin_amdgcn_raw_buffer_store_b64((i32x2){__builtin_bit_cast(int, v0), __builtin_bit_cast(int, v1)}, ry, off2, so, 0);
+                if (edge_tile) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v0), ry, off1, so, 0);
+            }
+        }
+    }
+}
 
 struct FirParams {
     const float* x;  // [NC][H][W]

@@ -16,20 +16,15 @@ __global__ __launch_bounds__(256, 3) void k_modconv(ConvParams p) {
     __shared__ float ws[2][KC * WROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave & 1, wp = wave >> 1, half = lane >> 5, j = lane & 31;
-    const int tiles_x = (p.GW + CONV_TW - 1) / CONV_TW;
-    const int gy0 = (blockIdx.x / tiles_x) * CONV_TH, gx0 = (blockIdx.x % tiles_x) * CONV_TW;
-    const int o0 = blockIdx.y * 64;
-    const int n = blockIdx.z / p.ksplit, kz = blockIdx.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
+    const ConvTile tl = conv_tile16(p);
+    const int gy0 = tl.gy0, gx0 = tl.gx0, o0 = tl.o0;
+    const ConvSlice sl = conv_slice(p, blockIdx.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, ic_end = sl.ic_end;
     const float* xn = p.x + (size_t)n * p.I * p.H * p.W;
     const float* sn = p.styles + (size_t)n * p.I;
 
     f32x16 acc[NB];
-#pragma unroll
-    for (int t = 0; t < NB; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    conv_zero(acc);
     const int prow0 = (CONV_TH / 2) * wp + (j >> 4), pcol = j & 15;
     // lane bases of the two LDS operands: this lane's pixel (+ the halo origin) and its k half
     const int xlane = (prow0 + 1) * XS_ROW + pcol + 1 + half * XS_PLANE;
@@ -67,23 +62,16 @@ __global__ __launch_bounds__(256, 3) void k_modconv(ConvParams p) {
         buf ^= 1;
     }
     // ---- epilogue (ksplit > 1: raw partial sums into slice kz of the partial buffer)
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0);
+    float* yout = conv_yout(p, sl.kz);
 #pragma unroll
     for (int t = 0; t < NB; ++t) {
         const int gy = gy0 + prow0 + 2 * t, gx = gx0 + pcol;
         if (gy >= p.GH || gx >= p.GW) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int ch = o0 + wc * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int ch = o0 + wc * 32 + conv_acc_ch(r, half);
             if (ch >= p.O) continue;
-            float v = acc[t][r];
-            if (p.epilogue) {
-                if (p.dcoef) v = v * p.dcoef[(size_t)n * p.O + ch];
-                if (p.noise) v = v + p.noise[(p.noise_per_sample ? (size_t)n * p.OH * p.OW : 0) + (size_t)gy * p.OW + gx];
-                if (p.bias) v = v + p.bias[ch];
-                v = act_apply(v, p.act, p.alpha, p.gain, p.clamp);
-            }
-            yout[(((size_t)n * p.O + ch) * p.OH + gy) * p.OW + gx] = v;
+            conv_epilogue_store(p, yout, n, ch, gy, gx, acc[t][r]);
         }
     }
 }
@@ -96,20 +84,15 @@ __global__ __launch_bounds__(256, 2) void k_modconv_h(ConvParams p) {
     __shared__ __attribute__((aligned(16))) char ws[SPLIT ? 1 : 2][SPLIT ? 2 * WBYTES : WBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave & 1, wp = wave >> 1, half = lane >> 5, j = lane & 31;
-    const int tiles_x = (p.GW + CONV_TW - 1) / CONV_TW;
-    const int gy0 = (blockIdx.x / tiles_x) * CONV_TH, gx0 = (blockIdx.x % tiles_x) * CONV_TW;
-    const int o0 = blockIdx.y * 64;
-    const int n = blockIdx.z / p.ksplit, kz = blockIdx.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
+    const ConvTile tl = conv_tile16(p);
+    const int gy0 = tl.gy0, gx0 = tl.gx0, o0 = tl.o0;
+    const ConvSlice sl = conv_slice(p, blockIdx.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, ic_end = sl.ic_end;
     const float* xn = p.x + (size_t)n * p.I * p.H * p.W;
     const float* sn = p.styles + (size_t)n * p.I;
 
     f32x16 acc[NB];
-#pragma unroll
-    for (int t = 0; t < NB; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    conv_zero(acc);
     const int prow0 = (CONV_TH / 2) * wp + (j >> 4), pcol = j & 15;
     const int xlane = half * HX_HALF + ((prow0 + 1) * HX_PITCH + pcol + 1) * 16;  // bytes
     const int wlane = (half * 64 + wc * 32 + j) * 16;
@@ -162,24 +145,16 @@ __global__ __launch_bounds__(256, 2) void k_modconv_h(ConvParams p) {
         __syncthreads();
         buf ^= 1;
     }
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0);
+    float* yout = conv_yout(p, sl.kz);
 #pragma unroll
     for (int t = 0; t < NB; ++t) {
         const int gy = gy0 + prow0 + 2 * t, gx = gx0 + pcol;
         if (gy >= p.GH || gx >= p.GW) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int ch = o0 + wc * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int ch = o0 + wc * 32 + conv_acc_ch(r, half);
             if (ch >= p.O) continue;
-            float v = acc[t][r];
-            if constexpr (SPLIT) v *= HX_SPLIT_UNSCALE;
-            if (p.epilogue) {
-                if (p.dcoef) v = v * p.dcoef[(size_t)n * p.O + ch];
-                if (p.noise) v = v + p.noise[(p.noise_per_sample ? (size_t)n * p.OH * p.OW : 0) + (size_t)gy * p.OW + gx];
-                if (p.bias) v = v + p.bias[ch];
-                v = act_apply(v, p.act, p.alpha, p.gain, p.clamp);
-            }
-            yout[(((size_t)n * p.O + ch) * p.OH + gy) * p.OW + gx] = v;
+            conv_epilogue_store(p, yout, n, ch, gy, gx, SPLIT ? acc[t][r] * HX_SPLIT_UNSCALE : acc[t][r]);
         }
     }
 }
@@ -194,19 +169,13 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w2(ConvParams p) {
     const int tiles_x = (p.GW + WX_TW - 1) / WX_TW;
     const int gy0 = (blockIdx.x / tiles_x) * CONV_TH, gx0 = (blockIdx.x % tiles_x) * WX_TW;
     const int o0 = blockIdx.y * 64;
-    const int n = blockIdx.z / p.ksplit, kz = blockIdx.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
+    const ConvSlice sl = conv_slice(p, blockIdx.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, ic_end = sl.ic_end;
     const float* xn = p.x + (size_t)n * p.I * p.H * p.W;
     const float* sn = p.styles + (size_t)n * p.I;
 
     f32x16 acc[2][2];  // [channel tile][row of the wave's row pair]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    conv_zero(acc);
     // a B tile is ONE row of 32 columns (lane j = column j): ds_read_b128 serves lanes {0-3, 12-15, 20-27} together, and with
     // 2 rows x 16 columns per tile the 34-pixel row pitch put lanes 20-27 on the slots of lanes 12-13 (35 % conflict cycles)
     const int prow = 2 * wave, pcol = j;
@@ -217,12 +186,9 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w2(ConvParams p) {
     if constexpr (IMG) {  // piece offsets inside the chunk-relative image slice
 #pragma unroll
         for (int u = 0; u < WX_ROUNDS; ++u) {
-            const int it = tid + u * 256;
+            const int it = tid + u * 256;  // item = (k half h, pixel px of the 10 x 34 patch)
             const int h = it / ((CONV_TH + 2) * WX_ROW), px = it - h * ((CONV_TH + 2) * WX_ROW);
-            const int r = px / WX_ROW, c = px - r * WX_ROW;
-            const int iy = gy0 - 1 + r, ix = gx0 - 1 + c;
-            const bool ok = it < WX_ITEMS && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            pl.xoff[u] = ok ? ((h * p.H + iy) * p.W + ix) * 16 : CONV_OOB;
+            pl.xoff[u] = conv_patch_voff(p, px, it < WX_ITEMS, WX_ROW, gy0, gx0, h);
         }
     }
     ConvStageRegsW rg;
@@ -301,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w2(ConvParams p) {
         if (more) conv_glds_wh(p, pl, ws, tid, ic0 + 16, ic_end, 1);
         buf ^= 1;
     }
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0);
+    float* yout = conv_yout(p, sl.kz);
     const int gx = gx0 + pcol;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -311,16 +277,9 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w2(ConvParams p) {
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ch = o0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int ch = o0 + a * 32 + conv_acc_ch(r, half);
                 if (ch >= p.O) continue;
-                float v = acc[a][b][r] * HX_SPLIT_UNSCALE;
-                if (p.epilogue) {
-                    if (p.dcoef) v = v * p.dcoef[(size_t)n * p.O + ch];
-                    if (p.noise) v = v + p.noise[(p.noise_per_sample ? (size_t)n * p.OH * p.OW : 0) + (size_t)gy * p.OW + gx];
-                    if (p.bias) v = v + p.bias[ch];
-                    v = act_apply(v, p.act, p.alpha, p.gain, p.clamp);
-                }
-                yout[(((size_t)n * p.O + ch) * p.OH + gy) * p.OW + gx] = v;
+                conv_epilogue_store(p, yout, n, ch, gy, gx, acc[a][b][r] * HX_SPLIT_UNSCALE);
             }
     }
 }
@@ -365,10 +324,8 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w3(ConvParams p) {
     const WgOrder wo = p3d_wg_order(p.xcd != 0);
     const int gy0 = (wo.tile / tiles_x) * CONV_TH, gx0 = (wo.tile % tiles_x) * WX_TW;
     const int o0 = wo.otile * 64;
-    const int n = wo.z / p.ksplit, kz = wo.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
-    const int nch = ic_end > ic_beg ? (ic_end - ic_beg) >> 4 : 0;
+    const ConvSlice sl = conv_slice(p, wo.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, nch = sl.nch;
     const int HW = p.H * p.W;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
 
@@ -393,15 +350,9 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w3(ConvParams p) {
     const int sub_which = wave >> 1, sub_kh = wave & 1;
     int pvoff[6];
 #pragma unroll
-    for (int u = 0; u < 6; ++u) {
-        const int it = u * 64 + lane;
-        const int r = it / WX_ROW, c = it - r * WX_ROW;
-        const int iy = gy0 - 1 + r, ix = gx0 - 1 + c;
-        const bool ok = it < (CONV_TH + 2) * WX_ROW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        pvoff[u] = ok ? ((sub_kh * p.H + iy) * p.W + ix) * 16 : CONV_OOB;
-    }
+    for (int u = 0; u < 6; ++u) pvoff[u] = conv_patch_voff(p, u * 64 + lane, u * 64 + lane < (CONV_TH + 2) * WX_ROW, WX_ROW, gy0, gx0, sub_kh);
     const bool last_lanes = lane < (CONV_TH + 2) * WX_ROW - 5 * 64;  // the sixth instruction covers items 320 .. 339
-    const char* img_base = (const char*)p.ximg + (sub_which ? p.ximg_lo : 0) + (size_t)n * (p.I >> 3) * HW * 16;
+    const char* img_base = conv_img_base(p, HW, n, sub_which);
     // chunk >= nch: a zero-length resource (zeros, no traffic, same instruction count)
     auto patch_rsrc = [&](int chunk) {
         const bool in = chunk < nch;
@@ -436,12 +387,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w3(ConvParams p) {
     };
 
     f32x16 acc[2][2];  // [channel tile][row of the wave's row pair]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    conv_zero(acc);
     const int prow = 2 * wave;
     const int blane = half * W3_SUB + (prow * WX_ROW + j) * 16;  // patch row prow, column j of this lane's k half (hi image)
     const int alane = (half * 64 + j) * 16;
@@ -522,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_w3(ConvParams p) {
     const bool ep = p.epilogue != 0;
     const float alpha = (ep && p.act == 1) ? p.alpha : 1.0f, gain = ep ? p.gain : 1.0f;
     const float cl = (ep && p.clamp >= 0.0f) ? p.clamp : __builtin_inff();
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0) + (size_t)n * p.O * p.OH * p.OW;
+    float* yout = conv_yout(p, sl.kz) + (size_t)n * p.O * p.OH * p.OW;
     const int OHW = p.OH * p.OW;
     auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, p.O * OHW * 4, CONV_RSRC_FLAGS);
     const int gx = gx0 + j;

@@ -1,8 +1,28 @@
-// p3d_conv_stage.hpp — staging helpers of the register-staged convolution kernels (fp32 operands, f16 / two-term operands on the
-// 8 x 16 tile, two-term operands on the 8 x 32 tile, the activation-image DMA of k_modconv_w2): shared by the plain
-// (p3d_conv_plain.hip) and the transposed (p3d_conv_up.hip) kernels.
+// p3d_conv_stage.hpp — what the register-staged convolution kernels share: their 8 x 16 tile origin (conv_tile16), the ordinary
+// epilogue (conv_epilogue_store) and the staging helpers (fp32 operands, f16 / two-term operands on the 8 x 16 tile, two-term
+// operands on the 8 x 32 tile, the activation-image DMA of k_modconv_w2).  Included by the plain (p3d_conv_plain.hip) and the
+// transposed (p3d_conv_up.hip) kernels; the steps the image-fed kernels share as well are in p3d_conv_common.hpp.
 #pragma once
 #include "p3d_conv_common.hpp"
+
+// tile origin of the kernels on the CONV_TH x CONV_TW tile: blockIdx.x = tile (row-major), blockIdx.y = 64-channel tile
+struct ConvTile { int gy0, gx0, o0; };
+DEV ConvTile conv_tile16(const ConvParams& p) {
+    const int tiles_x = (p.GW + CONV_TW - 1) / CONV_TW;
+    return {(int)(blockIdx.x / tiles_x) * CONV_TH, (int)(blockIdx.x % tiles_x) * CONV_TW, (int)blockIdx.y * 64};
+}
+// The ordinary epilogue of one output value (p.epilogue: demodulation, noise, bias, activation — in this order, -ffp-contract=off;
+// else raw: a transposed-conv intermediate or a split-K partial) and its store; yout = conv_yout(p, kz)
+DEV void conv_epilogue_store(const ConvParams& p, float* yout, int n, int ch, int gy, int gx, float v) {
+    const size_t px = (size_t)gy * p.OW + gx;  // the pixel's part of the noise index
+    if (p.epilogue) {
+        if (p.dcoef) v = v * p.dcoef[(size_t)n * p.O + ch];
+        if (p.noise) v = v + p.noise[(p.noise_per_sample ? (size_t)n * p.OH * p.OW : 0) + px];
+        if (p.bias) v = v + p.bias[ch];
+        v = act_apply(v, p.act, p.alpha, p.gain, p.clamp);
+    }
+    yout[(((size_t)n * p.O + ch) * p.OH + gy) * p.OW + gx] = v;
+}
 
 // =====================================================================================================================
 // The convolution kernels.  The f32 MFMA shares its SIMD with the VALU (tools/ubench/mfma_valu_overlap.hip), so the K loop is

@@ -19,22 +19,15 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up(ConvParams p) {
     __shared__ float ws[2][KC * WROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave & 1, wp = wave >> 1, half = lane >> 5, j = lane & 31;
-    const int tiles_x = (p.GW + CONV_TW - 1) / CONV_TW;
-    const int gy0 = (blockIdx.x / tiles_x) * CONV_TH, gx0 = (blockIdx.x % tiles_x) * CONV_TW;
-    const int o0 = blockIdx.y * 64;
-    const int n = blockIdx.z / p.ksplit, kz = blockIdx.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
+    const ConvTile tl = conv_tile16(p);
+    const int gy0 = tl.gy0, gx0 = tl.gx0, o0 = tl.o0;
+    const ConvSlice sl = conv_slice(p, blockIdx.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, ic_end = sl.ic_end;
     const float* xn = p.x + (size_t)n * p.I * p.H * p.W;
     const float* sn = p.styles + (size_t)n * p.I;
 
     f32x16 acc[4][2];  // [phase = 2*py + px][N tile]
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ph][t][r] = 0.0f;
+    conv_zero(acc);
     const int prow0 = 4 * wp + (j >> 4), pcol = j & 15;
     const int xlane = (prow0 + 1) * XS_ROW + pcol + 1 + half * XS_PLANE;
     const int wlane = wc * 32 + j + half * NT * WROW;
@@ -86,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up(ConvParams p) {
         buf ^= 1;
     }
     // ---- raw store of the four phases (ksplit > 1: into slice kz of the partial buffer); the FIR pass applies the epilogue
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0);
+    float* yout = conv_yout(p, sl.kz);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int gy = gy0 + prow0 + 2 * t, gx = gx0 + pcol;
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up(ConvParams p) {
             const int oy = 2 * gy + py, ox = 2 * gx + px;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ch = o0 + wc * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int ch = o0 + wc * 32 + conv_acc_ch(r, half);
                 if (ch < p.O) yout[(((size_t)n * p.O + ch) * p.OH + oy) * p.OW + ox + p.tox] = acc[ph][t][r];
             }
         }
@@ -140,10 +133,8 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
     const int gy0 = FUSED ? (wo.tile / tiles_x) * 6 - 1 : (wo.tile / tiles_x) * 8;
     const int gx0 = FUSED ? (wo.tile % tiles_x) * 30 - 1 : (wo.tile % tiles_x) * WX_TW;
     const int o0 = wo.otile * 32;
-    const int n = wo.z / p.ksplit, kz = wo.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
-    const int nch = ic_end > ic_beg ? (ic_end - ic_beg) >> 4 : 0;
+    const ConvSlice sl = conv_slice(p, wo.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, nch = sl.nch;
     const int HW = p.H * p.W;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
     // FUSED: the epilogue's per-channel constants (read after the K loop's barriers) and this thread's twelve noise values, requested
@@ -169,27 +160,15 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
     const int sub_which = wave >> 1, sub_kh = wave & 1;
     int pvoff[5];
 #pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        const int it = u * 64 + lane;
-        const int r = it / WX_ROW, c = it - r * WX_ROW;
-        const int iy = gy0 - 1 + r, ix = gx0 - 1 + c;
-        const bool ok = it < U3_ROWS * WX_ROW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        pvoff[u] = ok ? ((sub_kh * p.H + iy) * p.W + ix) * 16 : CONV_OOB;
-    }
+    for (int u = 0; u < 5; ++u) pvoff[u] = conv_patch_voff(p, u * 64 + lane, u * 64 + lane < U3_ROWS * WX_ROW, WX_ROW, gy0, gx0, sub_kh);
     const bool last_lanes = lane < U3_ROWS * WX_ROW - 4 * 64;
-    const char* img_base = (const char*)p.ximg + (sub_which ? p.ximg_lo : 0) + (size_t)n * (p.I >> 3) * HW * 16;
+    const char* img_base = conv_img_base(p, HW, n, sub_which);
     // Weights: 1152 pieces (hi|lo, tap, k half, o) = 18 instructions; wave w issues instructions w, w + 4, ...
     const int LO = p.O * 9 * p.I * 2;
     const bool wlds = p.wlayout == P3D_WLAYOUT_UP;
     int wvoff[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int q = (wave + 4 * i) * 64 + lane, which = q / 576, rem = q - which * 576;
-        const int tap = rem >> 6, kh = (rem >> 5) & 1, o = rem & 31;
-        // P3D_WLAYOUT_UP: the weights arrive as this kernel's LDS image [chunk][O/32][hi|lo][tap][k half][32 o][8] (18 KB of consecutive bytes
-        // per chunk and channel tile, a request = 1 KB of them); else 16-byte pieces gathered out of [hi|lo][O][9][I]
-        wvoff[i] = q >= 1152 ? CONV_OOB : wlds ? q * 16 : (o0 + o < p.O) ? which * LO + (((o0 + o) * 9 + tap) * p.I + 8 * kh) * 2 : CONV_OOB;
-    }
+    for (int i = 0; i < 5; ++i) wvoff[i] = up_weight_voff<4>(p, LO, wave, lane, i, o0, wlds);
     const bool five = wave < 2;  // instructions 16, 17 exist for waves 0, 1 only
     // piece i of chunk `chunk` into buffer `buf`: 0 .. 4 the patch (4: partial), 5 .. 9 the weights (9: waves 0, 1).  chunk >= nch: a
     // zero-length resource (zeros into the idle buffer, no traffic, the same instruction count)
@@ -213,17 +192,10 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
     };
 
     f32x16 acc[4][2];  // [phase = 2 py + px][row of the wave's pair]
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ph][t][r] = 0.0f;
+    conv_zero(acc);
     // patch row 2w + 1 + t is grid row gy0 + 2w + t; column j + 1 is grid column gx0 + j
     const int blane = half * U3_SUB + ((2 * wave) * WX_ROW + j) * 16;
     const int alane = (half * 32 + j) * 16;
-    // (phase, tap, input) of the nine products: input 0 = x[y][x], 1 = x[y][x-1], 2 = x[y-1][x], 3 = x[y-1][x-1]
-    const int PH[9] = {0, 1, 2, 3, 0, 2, 0, 1, 0}, TP[9] = {0, 1, 3, 4, 2, 5, 6, 7, 8}, BO[9] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
 
     {
         const U3Rs r0 = rsrcs(0);
@@ -259,14 +231,14 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
 #pragma unroll
                 for (int q = 0; q < 9; ++q) {
                     if (!((QM >> q) & 1)) continue;
-                    const f16x8 ah = *reinterpret_cast<const f16x8*>(wb + TP[q] * 64 * 16);
-                    const f16x8 al = *reinterpret_cast<const f16x8*>(wb + (9 + TP[q]) * 64 * 16);
+                    const f16x8 ah = *reinterpret_cast<const f16x8*>(wb + UpTaps::TP[q] * 64 * 16);
+                    const f16x8 al = *reinterpret_cast<const f16x8*>(wb + (9 + UpTaps::TP[q]) * 64 * 16);
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
-                        const int r = 1 + t - (BO[q] >> 1), c = 1 - (BO[q] & 1);
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[r][c], acc[PH[q]][t], 0, 0, 0);
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[r][c], acc[PH[q]][t], 0, 0, 0);
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[r][c], acc[PH[q]][t], 0, 0, 0);
+                        const int r = 1 + t - (UpTaps::BO[q] >> 1), c = 1 - (UpTaps::BO[q] & 1);
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
                         // a full tile issues the next chunk's ten pieces two at a time under the MFMAs of its first five taps
                         if (FULL && t == 0 && q < 5) {
                             __builtin_amdgcn_sched_barrier(0);
@@ -316,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
                     for (int ph = 0; ph < 4; ++ph)
 #pragma unroll
                         for (int rr = 0; rr < 8; ++rr)
-                            T[((rr & 3) + 8 * (rr >> 2) + 4 * half) * U3F_PS + (2 * (2 * wave + t) + (ph >> 1)) * 64 + 2 * j + (ph & 1)] =
+                            T[conv_acc_ch(rr, half) * U3F_PS + (2 * (2 * wave + t) + (ph >> 1)) * 64 + 2 * j + (ph & 1)] =
                                 acc[ph][t][rr] * HX_SPLIT_UNSCALE;
             } else {
 #pragma unroll
@@ -325,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
                     for (int ph = 0; ph < 4; ++ph)
 #pragma unroll
                         for (int rr = 0; rr < 8; ++rr)
-                            T[((rr & 3) + 8 * (rr >> 2) + 4 * half) * U3F_PS + (2 * (2 * wave + t) + (ph >> 1)) * 64 + 2 * j + (ph & 1)] =
+                            T[conv_acc_ch(rr, half) * U3F_PS + (2 * (2 * wave + t) + (ph >> 1)) * 64 + 2 * j + (ph & 1)] =
                                 acc[ph][t][8 + rr] * HX_SPLIT_UNSCALE;
             }
             __syncthreads();
@@ -385,32 +357,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up3(ConvParams p) {
         if (bad && p.sat) atomicOr(p.sat, 1u);
         return;
     }
-    // ---- raw store: a lane owns both column phases (ox = 2 gx, 2 gx + 1) of its grid point: one 8-byte store per (row phase, channel),
-    // 32 lanes = 256 contiguous bytes; the last grid column (gx = W) has only px = 0: a 4-byte store of its own
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0) + (size_t)n * p.O * p.OH * p.OW;
-    const int OHW = p.OH * p.OW;
-    auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, p.O * OHW * 4, CONV_RSRC_FLAGS);
-    const int gx = gx0 + j;
-    const bool edge_tile = gx0 + WX_TW > p.W;  // (uniform) this tile holds the column gx = W
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int gy = gy0 + 2 * wave + t;
-#pragma unroll
-        for (int py = 0; py < 2; ++py) {
-            const bool row_ok = gy <= p.H - py;
-            const int base = ((o0 + 4 * half) * OHW + (2 * gy + py) * p.OW + 2 * gx + p.tox) * 4;
-            const int off2 = (row_ok && gx < p.W && o0 + 4 * half < p.O) ? base : CONV_OOB;
-            const int off1 = (row_ok && gx == p.W && o0 + 4 * half < p.O) ? base : CONV_OOB;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int so = ((r & 3) + 8 * (r >> 2)) * OHW * 4;
-                const float v0 = acc[2 * py][t][r] * HX_SPLIT_UNSCALE, v1 = acc[2 * py + 1][t][r] * HX_SPLIT_UNSCALE;
-                typedef int i32x2 __attribute__((ext_vector_type(2)));
-                __builtin_amdgcn_raw_buffer_store_b64((i32x2){__builtin_bit_cast(int, v0), __builtin_bit_cast(int, v1)}, ry, off2, so, 0);
-                if (edge_tile) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v0), ry, off1, so, 0);
-            }
-        }
-    }
+    up_store_phases(p, acc, sl, o0, gy0, gx0, wave, half, j);  // the intermediate or split-K partials; the FIR pass applies the epilogue
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -476,10 +423,8 @@ __global__ __launch_bounds__(512, 2) void k_modconv_up5(ConvParams p) {
     }
     const int gy0 = (tile / tiles_x) * 8, gx0 = (tile % tiles_x) * WX_TW;
     const int o0 = otile * 32;
-    const int n = zz / p.ksplit, kz = zz - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
-    const int nch = ic_end > ic_beg ? (ic_end - ic_beg) >> 4 : 0;
+    const ConvSlice sl = conv_slice(p, zz);
+    const int n = sl.n, ic_beg = sl.ic_beg, nch = sl.nch;
     const int HW = p.H * p.W;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
     const bool col_edge = gx0 == p.W, row_edge = gy0 == p.H;  // (uniform) the light tiles of the (H + 1) x (W + 1) grid
@@ -488,24 +433,16 @@ __global__ __launch_bounds__(512, 2) void k_modconv_up5(ConvParams p) {
         const int sub_which = wave >> 1, sub_kh = wave & 1;
         int pvoff[5];
 #pragma unroll
-        for (int u = 0; u < 5; ++u) {
-            const int it = u * 64 + lane;
-            const int r = it / U5_PW, c = it - r * U5_PW;
-            const int iy = gy0 - 1 + r, ix = gx0 - 1 + c;
-            pvoff[u] = (it < 9 * U5_PW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) ? ((sub_kh * p.H + iy) * p.W + ix) * 16 : CONV_OOB;
-        }
-        const char* img_base = (const char*)p.ximg + (sub_which ? p.ximg_lo : 0) + (size_t)n * (p.I >> 3) * HW * 16;
+        for (int u = 0; u < 5; ++u) pvoff[u] = conv_patch_voff(p, u * 64 + lane, u * 64 + lane < 9 * U5_PW, U5_PW, gy0, gx0, sub_kh);
+        const char* img_base = conv_img_base(p, HW, n, sub_which);
         // Weights: 1152 pieces (hi|lo, tap, k half, o) = 18 requests; wave 4 + s issues requests s, s + 4, ... (the fifth round: s = 0, 1)
         const int LO = p.O * 9 * p.I * 2;
         const bool wlds = p.wlayout == P3D_WLAYOUT_UP;
         int wvoff[5];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int q = (wave + 4 * i) * 64 + lane, which = q / 576, rem = q - which * 576;
-            const int tap = rem >> 6, kh = (rem >> 5) & 1, o = rem & 31;
-            wvoff[i] = q >= 1152 ? CONV_OOB : wlds ? q * 16 : (o0 + o < p.O) ? which * LO + (((o0 + o) * 9 + tap) * p.I + 8 * kh) * 2 : CONV_OOB;
-        }
+        for (int i = 0; i < 5; ++i) wvoff[i] = up_weight_voff<4>(p, LO, wave, lane, i, o0, wlds);
         const bool five = wave < 2;
+        // chunk >= nch: zero-length resources (zeros into an idle buffer, no traffic, the same request count)
         // chunk >= nch: zero-length resources (zeros into an idle buffer, no traffic, the same request count)
         auto patch_rsrc = [&](int chunk) {
             const bool in = chunk < nch;
@@ -554,16 +491,9 @@ __global__ __launch_bounds__(512, 2) void k_modconv_up5(ConvParams p) {
 
     // ---- the multiplying waves
     f32x16 acc[4][2];  // [phase = 2 py + px][row of the wave's pair]
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ph][t][r] = 0.0f;
+    conv_zero(acc);
     const int blane = half * U5_SUB + ((2 * wave) * U5_PW + j) * 16;
     const int alane = (half * 32 + j) * 16;
-    // (phase, tap, input) of the nine products: input 0 = x[y][x], 1 = x[y][x-1], 2 = x[y-1][x], 3 = x[y-1][x-1] (k_modconv_up3's order)
-    const int PH[9] = {0, 1, 2, 3, 0, 2, 0, 1, 0}, TP[9] = {0, 1, 3, 4, 2, 5, 6, 7, 8}, BO[9] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
     __builtin_amdgcn_s_barrier();  // (the prologue's)
     auto run = [&](auto QMc, auto NTc, auto W0c) {
         constexpr int QM = decltype(QMc)::value, NT = decltype(NTc)::value;
@@ -588,23 +518,23 @@ __global__ __launch_bounds__(512, 2) void k_modconv_up5(ConvParams p) {
                 for (int q = 0; q < 9; ++q) {
                     if (!((QM >> q) & 1)) continue;
                     if ((1 << q) == QF) {
-                        ah[0] = *reinterpret_cast<const f16x8*>(wb + TP[q] * 64 * 16);
-                        al[0] = *reinterpret_cast<const f16x8*>(wb + (9 + TP[q]) * 64 * 16);
+                        ah[0] = *reinterpret_cast<const f16x8*>(wb + UpTaps::TP[q] * 64 * 16);
+                        al[0] = *reinterpret_cast<const f16x8*>(wb + (9 + UpTaps::TP[q]) * 64 * 16);
                     }
                     int qn = -1;  // the next valid tap: its weights are read under this tap's MFMAs
 #pragma unroll
                     for (int z = 8; z > q; --z)
                         if ((QM >> z) & 1) qn = z;
                     if (qn >= 0) {
-                        ah[cu ^ 1] = *reinterpret_cast<const f16x8*>(wb + TP[qn] * 64 * 16);
-                        al[cu ^ 1] = *reinterpret_cast<const f16x8*>(wb + (9 + TP[qn]) * 64 * 16);
+                        ah[cu ^ 1] = *reinterpret_cast<const f16x8*>(wb + UpTaps::TP[qn] * 64 * 16);
+                        al[cu ^ 1] = *reinterpret_cast<const f16x8*>(wb + (9 + UpTaps::TP[qn]) * 64 * 16);
                     }
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
-                        const int r = 1 + t - (BO[q] >> 1), c = 1 - (BO[q] & 1);
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cu], bl[r][c], acc[PH[q]][t], 0, 0, 0);
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cu], bh[r][c], acc[PH[q]][t], 0, 0, 0);
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cu], bh[r][c], acc[PH[q]][t], 0, 0, 0);
+                        const int r = 1 + t - (UpTaps::BO[q] >> 1), c = 1 - (UpTaps::BO[q] & 1);
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cu], bl[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cu], bh[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cu], bh[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
                     }
                     cu ^= 1;
                 }
@@ -619,32 +549,7 @@ __global__ __launch_bounds__(512, 2) void k_modconv_up5(ConvParams p) {
         else if (!col_edge) run(integral_constant<int, 0x1C0>{}, integral_constant<int, 1>{}, integral_constant<bool, true>{});
         else run(integral_constant<int, 0x100>{}, integral_constant<int, 1>{}, integral_constant<bool, true>{});
     }
-    // ---- raw store (k_modconv_up3's): a lane owns both column phases (ox = 2 gx, 2 gx + 1) of its grid point: one 8-byte store per
-    // (row phase, channel), 32 lanes = 256 contiguous bytes; the last grid column (gx = W) has only px = 0: a 4-byte store of its own
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0) + (size_t)n * p.O * p.OH * p.OW;
-    const int OHW = p.OH * p.OW;
-    auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, p.O * OHW * 4, CONV_RSRC_FLAGS);
-    const int gx = gx0 + j;
-    const bool edge_tile = gx0 + WX_TW > p.W;  // (uniform) this tile holds the column gx = W
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int gy = gy0 + 2 * wave + t;
-#pragma unroll
-        for (int py = 0; py < 2; ++py) {
-            const bool row_ok = gy <= p.H - py;
-            const int base = ((o0 + 4 * half) * OHW + (2 * gy + py) * p.OW + 2 * gx + p.tox) * 4;
-            const int off2 = (row_ok && gx < p.W && o0 + 4 * half < p.O) ? base : CONV_OOB;
-            const int off1 = (row_ok && gx == p.W && o0 + 4 * half < p.O) ? base : CONV_OOB;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int so = ((r & 3) + 8 * (r >> 2)) * OHW * 4;
-                const float v0 = acc[2 * py][t][r] * HX_SPLIT_UNSCALE, v1 = acc[2 * py + 1][t][r] * HX_SPLIT_UNSCALE;
-                typedef int i32x2 __attribute__((ext_vector_type(2)));
-                __builtin_amdgcn_raw_buffer_store_b64((i32x2){__builtin_bit_cast(int, v0), __builtin_bit_cast(int, v1)}, ry, off2, so, 0);
-                if (edge_tile) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v0), ry, off1, so, 0);
-            }
-        }
-    }
+    up_store_phases(p, acc, sl, o0, gy0, gx0, wave, half, j);  // (k_modconv_up3<false>'s store)
 }
 
 // the fused four-phase transposed convolution (see k_modconv_up) on f16 operands
@@ -655,22 +560,15 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
     __shared__ __attribute__((aligned(16))) char ws[SPLIT ? 1 : 2][SPLIT ? 2 * WBYTES : WBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave & 1, wp = wave >> 1, half = lane >> 5, j = lane & 31;
-    const int tiles_x = (p.GW + CONV_TW - 1) / CONV_TW;
-    const int gy0 = (blockIdx.x / tiles_x) * CONV_TH, gx0 = (blockIdx.x % tiles_x) * CONV_TW;
-    const int o0 = blockIdx.y * 64;
-    const int n = blockIdx.z / p.ksplit, kz = blockIdx.z - n * p.ksplit;
-    const int ic_per = ((p.I + p.ksplit - 1) / p.ksplit + 31) / 32 * 32;
-    const int ic_beg = kz * ic_per, ic_end = (ic_beg + ic_per < p.I) ? ic_beg + ic_per : p.I;
+    const ConvTile tl = conv_tile16(p);
+    const int gy0 = tl.gy0, gx0 = tl.gx0, o0 = tl.o0;
+    const ConvSlice sl = conv_slice(p, blockIdx.z);
+    const int n = sl.n, ic_beg = sl.ic_beg, ic_end = sl.ic_end;
     const float* xn = p.x + (size_t)n * p.I * p.H * p.W;
     const float* sn = p.styles + (size_t)n * p.I;
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ph][t][r] = 0.0f;
+    conv_zero(acc);
     const int prow0 = 4 * wp + (j >> 4), pcol = j & 15;
     const int xlane = half * HX_HALF + ((prow0 + 1) * HX_PITCH + pcol + 1) * 16;
     const int wlane = (half * 64 + wc * 32 + j) * 16;
@@ -689,8 +587,6 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
     }
     __syncthreads();
     int buf = 0;
-    // (phase, tap, patch offset) of the nine products of the four output phases
-    const int PH[9] = {0, 1, 2, 3, 0, 2, 0, 1, 0}, TP[9] = {0, 1, 3, 4, 2, 5, 6, 7, 8}, BO[9] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
     for (int ic0 = ic_beg; ic0 < ic_end; ic0 += 16) {
         const bool more = ic0 + 16 < ic_end;
         if (more) conv_gload_h<SPLIT ? 0 : NT, false>(p, pl, xn, sn, ic0 + 16, ic_end, rg);
@@ -712,9 +608,9 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
             load_b(boff, bq);
 #pragma unroll
             for (int q = 0; q < 9; ++q) {
-                const f16x8 a = *reinterpret_cast<const f16x8*>(wb + aoff + TP[q] * 128 * 16);
+                const f16x8 a = *reinterpret_cast<const f16x8*>(wb + aoff + UpTaps::TP[q] * 128 * 16);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bq[t][BO[q]], acc[PH[q]][t], 0, 0, 0);
+                for (int t = 0; t < 2; ++t) acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bq[t][UpTaps::BO[q]], acc[UpTaps::PH[q]][t], 0, 0, 0);
             }
         };
         if constexpr (SPLIT) {
@@ -728,11 +624,11 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
                 load_b(HX_BYTES, blq);
 #pragma unroll
                 for (int q = 0; q < 9; ++q) {
-                    const f16x8 a = *reinterpret_cast<const f16x8*>(wb + TP[q] * 128 * 16);
+                    const f16x8 a = *reinterpret_cast<const f16x8*>(wb + UpTaps::TP[q] * 128 * 16);
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, blq[t][BO[q]], acc[PH[q]][t], 0, 0, 0);  // a_hi x b_lo
-                        acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bhq[t][BO[q]], acc[PH[q]][t], 0, 0, 0);  // a_hi x b_hi
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, blq[t][UpTaps::BO[q]], acc[UpTaps::PH[q]][t], 0, 0, 0);  // a_hi x b_lo
+                        acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bhq[t][UpTaps::BO[q]], acc[UpTaps::PH[q]][t], 0, 0, 0);  // a_hi x b_hi
                     }
                 }
             }
@@ -743,9 +639,9 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
             if (more) conv_glds_w2<NT>(p, pl, ws[0], tid, ic0 + 16, ic_end, 0);
 #pragma unroll
             for (int q = 0; q < 9; ++q) {  // a_lo x b_hi
-                const f16x8 a = *reinterpret_cast<const f16x8*>(wb + WBYTES + TP[q] * 128 * 16);
+                const f16x8 a = *reinterpret_cast<const f16x8*>(wb + WBYTES + UpTaps::TP[q] * 128 * 16);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bhq[t][BO[q]], acc[PH[q]][t], 0, 0, 0);
+                for (int t = 0; t < 2; ++t) acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bhq[t][UpTaps::BO[q]], acc[UpTaps::PH[q]][t], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(0);
@@ -759,7 +655,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
         }
         buf ^= 1;
     }
-    float* yout = p.y + (p.ksplit > 1 ? (size_t)kz * p.N * p.O * p.OH * p.OW : 0);
+    float* yout = conv_yout(p, sl.kz);
     // a lane owns both column phases (ox = 2 gx, 2 gx + 1) of its grid point: one 8-byte store per (row phase, channel) — 16 lanes
     // cover 128 contiguous bytes of an output row — instead of two 4-byte stores 8 bytes apart (the last grid column has only
     // px = 0; rows of the odd-width intermediate are 4-byte aligned, which global stores allow)
@@ -774,7 +670,7 @@ __global__ __launch_bounds__(256, 2) void k_modconv_up_h(ConvParams p) {
             const bool both = gx < p.W;  // px = 1 exists
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ch = o0 + wc * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int ch = o0 + wc * 32 + conv_acc_ch(r, half);
                 if (ch >= p.O) continue;
                 const float v0 = SPLIT ? acc[2 * py][t][r] * HX_SPLIT_UNSCALE : acc[2 * py][t][r];
                 const float v1 = SPLIT ? acc[2 * py + 1][t][r] * HX_SPLIT_UNSCALE : acc[2 * py + 1][t][r];

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
     const int gy0 = (wo.tile / tiles_x) * (C::GR - 2) - 1, gx0 = (wo.tile % tiles_x) * 30 - 1;
     const int o0 = wo.otile * 32;
     const int n = wo.z;
-    const int nch = p.I >> 4;
+    const int nch = p.I >> 4;  // (unsplit: the whole K range)
     const int HW = p.H * p.W;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
 
@@ -84,22 +84,15 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
         // (eight waves, nine pieces: the second wave of a sub-image requests the last piece once more instead of skipping a turn — the same
         // bytes to the same place, and every wave issues the same number of requests: no branch in the K loop, one counted wait)
         const int pc = part + C::PARTS * i < C::NPS ? part + C::PARTS * i : C::NPS - 1;
-        const int it = pc * 64 + lane;
-        const int r = it / C::PW, c = it - r * C::PW;
-        const int iy = gy0 - 1 + r, ix = gx0 - 1 + c;
-        pvoff[i] = (it < C::ITEMS && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) ? ((sub_kh * p.H + iy) * p.W + ix) * 16 : CONV_OOB;
+        pvoff[i] = conv_patch_voff(p, pc * 64 + lane, pc * 64 + lane < C::ITEMS, C::PW, gy0, gx0, sub_kh);
     }
-    const char* img_base = (const char*)p.ximg + (sub_which ? p.ximg_lo : 0) + (size_t)n * (p.I >> 3) * HW * 16;
+    const char* img_base = conv_img_base(p, HW, n, sub_which);
     // Weights: 1152 pieces (hi|lo, tap, k half, o) = 18 instructions: wave w issues instructions w, w + NW, ... (the last round: waves 0, 1)
     const int LO = p.O * 9 * p.I * 2;
-    const bool wlds = p.wlayout == P3D_WLAYOUT_UP;
+    const bool wlds = p.wlayout == P3D_WLAYOUT_UP;  // (k_modconv_up3's image)
     int wvoff[C::WPW];
 #pragma unroll
-    for (int i = 0; i < C::WPW; ++i) {
-        const int q = (wave + NW * i) * 64 + lane, which = q / 576, rem = q - which * 576;
-        const int tap = rem >> 6, kh = (rem >> 5) & 1, o = rem & 31;
-        wvoff[i] = q >= 1152 ? CONV_OOB : wlds ? q * 16 : which * LO + (((o0 + o) * 9 + tap) * p.I + 8 * kh) * 2;  // (P3D_WLAYOUT_UP: k_modconv_up3's image)
-    }
+    for (int i = 0; i < C::WPW; ++i) wvoff[i] = up_weight_voff<NW>(p, LO, wave, lane, i, o0, wlds);
     // chunk >= nch: a zero-length resource (zeros into an idle buffer, no traffic, the same instruction count)
     auto patch_rsrc = [&](int chunk) {
         const bool in = chunk < nch;
@@ -136,6 +129,8 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
     };
 
     f32x16 acc[4][RPW];  // [phase = 2 py + px][row of the wave]
+    // (spelled out, not conv_zero: this kernel sits at the 256-register limit, and with the helper's form of the same zeroing the
+    // allocator spills two registers more in the FIR loop)
 #pragma unroll
     for (int ph = 0; ph < 4; ++ph)
 #pragma unroll
@@ -145,8 +140,6 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
     // patch row RPW w + 1 + t is grid row gy0 + RPW w + t; column j + 1 is grid column gx0 + j
     const int blane = half * C::SUB + ((RPW * wave) * C::PW + j) * 16;
     const int alane = (half * 32 + j) * 16;
-    // (phase, tap, input) of the nine products: input 0 = x[y][x], 1 = x[y][x-1], 2 = x[y-1][x], 3 = x[y-1][x-1] (k_modconv_up3's order)
-    const int PH[9] = {0, 1, 2, 3, 0, 2, 0, 1, 0}, TP[9] = {0, 1, 3, 4, 2, 5, 6, 7, 8}, BO[9] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
     // a wave whose grid rows all lie outside [0, H] (the first row of the top tiles, the rows below the map in the bottom tiles)
     // multiplies zeros only: it keeps its DMA duty and the barriers and leaves the matrix core to the others
     bool wave_active = false;
@@ -213,21 +206,21 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
                     bl[r][c] = *reinterpret_cast<const f16x8*>(pb + 2 * C::SUB + (r * C::PW + c) * 16);
                 }
             f16x8 ah[2], al[2];
-            ah[0] = *reinterpret_cast<const f16x8*>(wb + TP[0] * 64 * 16);
-            al[0] = *reinterpret_cast<const f16x8*>(wb + (9 + TP[0]) * 64 * 16);
+            ah[0] = *reinterpret_cast<const f16x8*>(wb + UpTaps::TP[0] * 64 * 16);
+            al[0] = *reinterpret_cast<const f16x8*>(wb + (9 + UpTaps::TP[0]) * 64 * 16);
 #pragma unroll
             for (int q = 0; q < 9; ++q) {
                 const int cur = q & 1;
                 if (q < 8) {  // the next tap's weights, read under this tap's MFMAs
-                    ah[cur ^ 1] = *reinterpret_cast<const f16x8*>(wb + TP[q + 1] * 64 * 16);
-                    al[cur ^ 1] = *reinterpret_cast<const f16x8*>(wb + (9 + TP[q + 1]) * 64 * 16);
+                    ah[cur ^ 1] = *reinterpret_cast<const f16x8*>(wb + UpTaps::TP[q + 1] * 64 * 16);
+                    al[cur ^ 1] = *reinterpret_cast<const f16x8*>(wb + (9 + UpTaps::TP[q + 1]) * 64 * 16);
                 }
 #pragma unroll
                 for (int t = 0; t < RPW; ++t) {
-                    const int r = 1 + t - (BO[q] >> 1), c = 1 - (BO[q] & 1);
-                    acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bl[r][c], acc[PH[q]][t], 0, 0, 0);
-                    acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cur], bh[r][c], acc[PH[q]][t], 0, 0, 0);
-                    acc[PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bh[r][c], acc[PH[q]][t], 0, 0, 0);
+                    const int r = 1 + t - (UpTaps::BO[q] >> 1), c = 1 - (UpTaps::BO[q] & 1);
+                    acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bl[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
+                    acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cur], bh[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
+                    acc[UpTaps::PH[q]][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bh[r][c], acc[UpTaps::PH[q]][t], 0, 0, 0);
                     if (t == 0) {
                         __builtin_amdgcn_sched_barrier(0);
                         issue(rw, wnext, rp, pnext, q);
@@ -283,7 +276,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
                     for (int ph = 0; ph < 4; ++ph)
 #pragma unroll
                         for (int rr = 0; rr < 8; ++rr)
-                            Tw[((rr & 3) + 8 * (rr >> 2)) * C::TPS + (2 * t + (ph >> 1)) * 64 + (ph & 1)] = acc[ph][t][rr] * HX_SPLIT_UNSCALE;
+                            Tw[conv_acc_ch(rr, 0) * C::TPS + (2 * t + (ph >> 1)) * 64 + (ph & 1)] = acc[ph][t][rr] * HX_SPLIT_UNSCALE;
             } else {
 #pragma unroll
                 for (int t = 0; t < RPW; ++t)
@@ -291,7 +284,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_modconv_up4(ConvParams p) {
                     for (int ph = 0; ph < 4; ++ph)
 #pragma unroll
                         for (int rr = 0; rr < 8; ++rr)
-                            Tw[((rr & 3) + 8 * (rr >> 2)) * C::TPS + (2 * t + (ph >> 1)) * 64 + (ph & 1)] = acc[ph][t][8 + rr] * HX_SPLIT_UNSCALE;
+                            Tw[conv_acc_ch(rr, 0) * C::TPS + (2 * t + (ph >> 1)) * 64 + (ph & 1)] = acc[ph][t][8 + rr] * HX_SPLIT_UNSCALE;
             }
         }
         __syncthreads();

@@ -21,6 +21,7 @@ import modconv_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+# (tools/modconv_bits.py imports SWITCHES, DEV, _dev, _weights_f16 and _call from this module: keep the names, or change the tool too)
 SWITCHES = ("P3D_UP4", "P3D_UP4_RPW", "P3D_UP3_FUSED", "P3D_UP5", "P3D_FIR_IMG2")
 GUARD = 1 << 16  # watched bytes past the reported workspace size
 

@@ -24,7 +24,7 @@ B = P._build
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"\(.*", "", x).replace("void ", "") for x in out[:len(names)]]
+    return [re.sub(r"\(.*", "", x.replace("(anonymous namespace)::", "")).replace("void ", "") for x in out[:len(names)]]
 
 
 def instruction_counts(path):
