@@ -136,6 +136,12 @@ PASTE_GRAD_SIGNATURES = {
     "p3d_paste_front_backward_workspace_bytes": (_Z, [_I, _I]),
     "p3d_paste_front_backward_f32": (_I, [C.POINTER(PasteGradArgs), _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_discriminator.h declares (the dual discriminator's layers)
+DISC_SIGNATURES = {
+    "p3d_conv2d_act_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "p3d_mbstd_f32": (_I, [_P, _I, _I, _L, _I, _I, _I, _P, _P, _P]),
+    "p3d_mbstd_backward_f32": (_I, [_P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _P]),
+}
 P3D_GRAD_STATS_BYTES = 256  # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
 
 _LIB = None
@@ -156,7 +162,7 @@ def lib():
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
-                + list(PASTE_GRAD_SIGNATURES.items()):
+                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

@@ -17,43 +17,9 @@
 
 #include "../../include/p3d_synthesis_grad.h"
 
-#define SG_TILE 64           // GEMM tile (rows x columns) per workgroup
-#define SG_KC 16             // K chunk staged through LDS
-#define SG_LD (SG_TILE + 4)  // LDS row pitch in floats
-#define SG_WG 256            // four waves, each a 32 x 32 quarter of the tile
-
-typedef float sg_f32x4 __attribute__((ext_vector_type(4)));
+#include "p3d_corr_tile.hpp"  // SG_* sizes, sg_mma_chunk, sg_corr_tile: shared with the forward convolution of p3d_discriminator.hip
 
 static inline size_t sg_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// ---- the matrix-core step shared by both GEMMs ------------------------------------------------------------------------------
-// As[k][m], Bs[k][n]: one K chunk.  Wave quarter (wm, wn); 2 x 2 blocks of v_mfma_f32_16x16x4_f32 (A[l&15][k=l>>4],
-// B[k=l>>4][l&15]; D col = l&15, row = 4*(l>>4) + r), four k steps per chunk in k order.
-__device__ __forceinline__ void sg_mma_chunk(const float (*As)[SG_LD], const float (*Bs)[SG_LD], sg_f32x4 (&acc)[2][2], int wm, int wn,
-                                             int lane) {
-#pragma unroll
-    for (int kk = 0; kk < SG_KC; kk += 4) {
-        const int k = kk + (lane >> 4), r = lane & 15;
-        const float a0 = As[k][wm + r], a1 = As[k][wm + 16 + r];
-        const float b0 = Bs[k][wn + r], b1 = Bs[k][wn + 16 + r];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ float sg_block_sum(float v, float* red) {
-    // fixed-order tree over the workgroup's SG_WG lanes
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = SG_WG / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // ---- bias_act backward ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float sg_gz(float y, float gy, int act, float alpha, float gain, float clamp) {
@@ -112,56 +78,11 @@ __global__ __launch_bounds__(SG_WG) void k_sg_noise_bwd(const float* __restrict_
 }
 
 // ---- data gradient ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SG_WG) void k_sg_dgrad(const float* __restrict__ g, int Ci, int Hi, int Wi, const float* __restrict__ wk,
-                                                    int taps, int Co, int Ho, int Wo, int stride, int pad, float* __restrict__ out) {
+__global__ __launch_bounds__(SG_WG) void k_sg_dgrad(SgCorr a, float* __restrict__ out) {
     __shared__ float As[SG_KC][SG_LD];
     __shared__ float Bs[SG_KC][SG_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int64_t P = (int64_t)Ho * Wo;
-    const int64_t p0 = (int64_t)blockIdx.x * SG_TILE;
-    const int co0 = blockIdx.y * SG_TILE;
-    const int64_t n = blockIdx.z;
-    const int64_t plane = (int64_t)Hi * Wi;
-    const float* gn = g + n * Ci * plane;
-    const int col = tid & 63, kr = tid >> 6;  // this lane stages column `col` of rows kr, kr + 4, kr + 8, kr + 12
-    const int64_t p = p0 + col;
-    const bool pin = p < P;
-    const int oy = pin ? (int)(p / Wo) : 0, ox = pin ? (int)(p % Wo) : 0;
-    const bool co_in = co0 + col < Co;
-    sg_f32x4 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = sg_f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < taps; ++t) {
-        const int ty = taps == 9 ? t / 3 : 0, tx = taps == 9 ? t % 3 : 0;
-        const int iy = stride * oy + ty - pad, ix = stride * ox + tx - pad;
-        const bool bin = pin && iy >= 0 && iy < Hi && ix >= 0 && ix < Wi;
-        const int64_t goff = bin ? (int64_t)iy * Wi + ix : 0;
-        const float* wt = wk + (int64_t)t * Ci * Co;
-        for (int ci0 = 0; ci0 < Ci; ci0 += SG_KC) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int kk = kr + 4 * j, ci = ci0 + kk;
-                As[kk][col] = (ci < Ci && co_in) ? wt[(int64_t)ci * Co + co0 + col] : 0.f;
-                Bs[kk][col] = (ci < Ci && bin) ? gn[(int64_t)ci * plane + goff] : 0.f;
-            }
-            __syncthreads();
-            sg_mma_chunk(As, Bs, acc, wm, wn, lane);
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wm + 16 * mi + 4 * (lane >> 4) + r;
-                const int64_t pc = p0 + wn + 16 * ni + (lane & 15);
-                if (co < Co && pc < P) out[(n * Co + co) * P + pc] = acc[mi][ni][r];
-            }
+    const int64_t P = (int64_t)a.Ho * a.Wo;
+    sg_corr_tile(a, As, Bs, [&](int64_t n, int co, int64_t pc, float v) { out[(n * a.Co + co) * P + pc] = v; });
 }
 
 // ---- modulation backward ----------------------------------------------------------------------------------------------------
@@ -335,8 +256,6 @@ __global__ __launch_bounds__(SG_WG) void k_sg_torgb_skip_bwd(const float* __rest
 }
 
 // ---- entry points -----------------------------------------------------------------------------------------------------------
-static const int64_t SG_MAX_GRID = 0x7fffffff;
-
 extern "C" int p3d_torgb_combine_backward_f32(const float* partial, int tiles, int N, int R, int H, int W, const float* bias, float clamp,
                                               const float* g_img, float* g_y, float* g_bias, const float* skip_fir, float* g_skip,
                                               void* stream) {
@@ -377,11 +296,10 @@ extern "C" int p3d_conv_dgrad_f32(const float* g, int N, int Ci, int Hi, int Wi,
     if (!g || !wk || !out) return P3D_E_ARG;
     if (N <= 0 || Ci <= 0 || Hi <= 0 || Wi <= 0 || Co <= 0 || Ho <= 0 || Wo <= 0) return P3D_E_ARG;
     if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2) || pad < 0 || pad > 2) return P3D_E_RANGE;
-    const int64_t P = (int64_t)Ho * Wo;
-    if ((P + SG_TILE - 1) / SG_TILE > SG_MAX_GRID || (Co + SG_TILE - 1) / SG_TILE > 65535 || N > 65535) return P3D_E_RANGE;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_sg_dgrad, dim3((unsigned)((P + SG_TILE - 1) / SG_TILE), (unsigned)((Co + SG_TILE - 1) / SG_TILE), (unsigned)N),
-                       dim3(SG_WG), 0, st, g, Ci, Hi, Wi, wk, taps, Co, Ho, Wo, stride, pad, out);
+    dim3 grid;
+    if (!sg_corr_grid(N, Co, Ho, Wo, &grid)) return P3D_E_RANGE;
+    const SgCorr a = {g, wk, Ci, Hi, Wi, taps, Co, Ho, Wo, stride, pad};
+    hipLaunchKernelGGL(k_sg_dgrad, grid, dim3(SG_WG), 0, (hipStream_t)stream, a, out);
     return (int)hipGetLastError();
 }
 

@@ -1430,3 +1430,187 @@ class _TorgbCombineFn(torch.autograd.Function):
         gs = mod_backward(x, styles, gx)
         dw, _ = conv_wgrad(gz, (1, 0, 0), x, styles, (1, 0, 0), 1, (H, W))
         return gx, dw.view(weight.shape), gs, gb, g_skip, None, None
+
+
+# ======================================================================================================================
+# The dual discriminator's operators (include/p3d_discriminator.h)
+# ======================================================================================================================
+def _conv2d_act_impl(x, wk, bias, act, gain, clamp, stride, pad, res, want_pre=False):
+    x, wk = _chk(x, "x"), _chk(wk, "wk")
+    if x.ndim != 4 or wk.ndim != 3 or wk.shape[1] != x.shape[1] or wk.shape[0] not in (1, 9):
+        raise RuntimeError("conv2d_act: x [N,Ci,H,W] and wk [taps (1 or 9),Ci,Co]")
+    if act not in _ACTS:
+        raise NotImplementedError(f"activation {act!r} is not used by the PAniC-3D discriminator")
+    idx, alpha, dg = _ACTS[act]
+    N, Ci, Hi, Wi = x.shape
+    taps, _, Co = wk.shape
+    k = 3 if taps == 9 else 1
+    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError("conv2d_act: the input is smaller than the kernel")
+    if bias is not None:
+        bias = _chk(bias, "bias")
+        if tuple(bias.shape) != (Co,):
+            raise RuntimeError("conv2d_act: bias must be [Co]")
+    if res is not None:
+        res = _chk(res, "res")
+        if tuple(res.shape) != (N, Co, Ho, Wo):
+            raise RuntimeError("conv2d_act: res must have the output's shape")
+    out = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=x.device)
+    pre = torch.empty_like(out) if want_pre else None
+    with _on(x.device):
+        rc = _lib.lib().p3d_conv2d_act_f32(_p(x), N, Ci, Hi, Wi, _p(wk), taps, Co, Ho, Wo, int(stride), int(pad), _p(bias), idx, float(alpha),
+                                           float(gain if gain is not None else dg), float(clamp if clamp is not None else -1), _p(res),
+                                           _p(pre), _p(out), _stream())
+    _lib.check(rc, "p3d_conv2d_act_f32")
+    return (out, pre) if want_pre else out
+
+
+def conv2d_act(x, wk, bias=None, act="linear", gain=None, clamp=None, stride=1, pad=0, res=None):
+    """Conv2dLayer's forward after any resampling, in one launch: clamp(act(corr(x, wk) + bias) * gain) (+ res).  x [N,Ci,H,W];
+    wk [taps,Ci,Co] = the layer's weight * weight_gain as weight.permute(2, 3, 1, 0); gain None = the activation's default.
+    A plain call under no_grad; records the HIP backward (first order only) when an input requires grad — same forward bits."""
+    if _wants_grad(x, wk, bias, res):
+        return _Conv2dActFn.apply(x, wk, bias, res, (act, gain, clamp, int(stride), int(pad)))
+    return _conv2d_act_impl(x, wk, bias, act, gain, clamp, int(stride), int(pad), res)
+
+
+R1_MESSAGE = ("the discriminator's HIP backward is first order only: the R1 penalty (r1_gamma > 0, the Dreg / Dboth phases) needs its "
+              "double backward, which is not implemented")
+
+
+def _first_order(backward):
+    """once_differentiable, with the failure moved to where it is understood: a backward that autograd itself records
+    (create_graph=True — the R1 penalty's torch.autograd.grad) raises at once instead of returning a graph that cannot be used."""
+    inner = torch.autograd.function.once_differentiable(backward)
+
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled():
+            raise RuntimeError(R1_MESSAGE)
+        return inner(ctx, *grads)
+    return wrapper
+
+
+_ONE_TAP = {}
+
+
+def _one_tap(device):
+    f = _ONE_TAP.get(device)
+    if f is None:
+        f = _ONE_TAP[device] = torch.ones((1, 1), dtype=torch.float32, device=device)
+    return f
+
+
+class _Conv2dActFn(torch.autograd.Function):
+    """Backward of one discriminator convolution layer: bias_act from the output before the residual, the data
+    gradient on p3d_conv_dgrad_f32 (flipped, transposed weights; a stride-2 layer's cotangent zero-interleaved first: the adjoint
+    of a stride-2 correlation is a stride-1 correlation over it), the weight gradient split over the output's pixels."""
+
+    @staticmethod
+    def forward(ctx, x, wk, bias, res, meta):
+        act, gain, clamp, stride, pad = meta
+        if res is not None:
+            y, pre = _conv2d_act_impl(x, wk, bias, act, gain, clamp, stride, pad, res, want_pre=True)
+        else:
+            y = pre = _conv2d_act_impl(x, wk, bias, act, gain, clamp, stride, pad, None)
+        ctx.meta = meta
+        ctx.save_for_backward(x, wk, pre)
+        return y
+
+    @staticmethod
+    @_first_order
+    def backward(ctx, gy):
+        x, wk, pre = ctx.saved_tensors
+        act, gain, clamp, stride, pad = ctx.meta
+        idx, alpha, dg = _ACTS[act]
+        gy = gy.contiguous()
+        gz, gb, _ = bias_act_backward(pre, gy, idx, alpha, float(gain if gain is not None else dg), clamp)
+        N, Ci, Hi, Wi = x.shape
+        taps, _, Co = wk.shape
+        k = 3 if taps == 9 else 1
+        Ho, Wo = gz.shape[-2:]
+        gx = gwk = None
+        if ctx.needs_input_grad[0]:
+            if k - 1 - pad < 0:
+                raise NotImplementedError("conv2d_act backward: pad > kernel_size - 1")
+            # gx[y] = sum_t gz[(y + pad - t) / stride] w[t] = sum_t' Z[y + t' - (k - 1 - pad)] w[k - 1 - t'], Z = gz with stride - 1 zeros
+            # between its values (positions past Z's end read 0, as Z's own continuation would)
+            Z = gz if stride == 1 else upfirdn2d(gz, _one_tap(gz.device), up=stride)
+            gx = conv_dgrad(Z, wk.detach().flip(0).transpose(1, 2).contiguous(), Ci, Hi, Wi, 1, k - 1 - pad)
+        if ctx.needs_input_grad[1]:
+            dw, _ = conv_wgrad(gz, (1, 0, 0), x.contiguous(), None, (stride, 1 if k == 3 else 0, pad), taps, (Ho, Wo))  # [taps,Co,Ci]
+            gwk = dw.transpose(1, 2).contiguous()
+        g_bias = gb.sum(0) if ctx.needs_input_grad[2] else None
+        return gx, gwk, g_bias, (gy if ctx.needs_input_grad[3] else None), None
+
+
+class _UpfirdnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, meta):
+        ctx.meta, ctx.hw = meta, tuple(x.shape[-2:])
+        return upfirdn2d(x, *meta)
+
+    @staticmethod
+    @_first_order
+    def backward(ctx, gy):
+        f, up, down, padding, flip_filter, gain = ctx.meta
+        return _upfirdn2d_adjoint(gy, f, up, down, padding, flip_filter, gain, ctx.hw), None
+
+
+def fir(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
+    """upfirdn2d for the discriminator: the plain call under no_grad, first-order differentiable in x (the adjoint is upfirdn2d with
+    up and down exchanged and the flipped filter, _upfirdn2d_adjoint) when x requires grad."""
+    if _wants_grad(x):
+        return _UpfirdnFn.apply(x, (f, up, down, padding, flip_filter, gain))
+    return upfirdn2d(x, f, up, down, padding, flip_filter, gain)
+
+
+def _mbstd_impl(x, group, F):
+    x = _chk(x, "x")
+    N, Cc, H, W = x.shape
+    G = N if group is None else min(int(group), N)
+    if N % G != 0 or Cc % F != 0:
+        raise RuntimeError("minibatch_std: the group size must divide the batch and num_channels the channels")
+    y = torch.empty((N, Cc + F, H, W), dtype=torch.float32, device=x.device)
+    sd = torch.empty((N // G, Cc, H, W), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.lib().p3d_mbstd_f32(_p(x), N, Cc, H * W, G, int(F), 1, _p(y), _p(sd), _stream())
+    _lib.check(rc, "p3d_mbstd_f32")
+    return y, sd, G
+
+
+def minibatch_std(x, group_size, num_channels=1):
+    """MinibatchStdLayer.forward (networks_stylegan2.py:854-869): x [N,C,H,W] -> [N,C+F,H,W].  Plain under no_grad, a first-order
+    autograd function when x requires grad — same forward bits."""
+    if _wants_grad(x):
+        return _MbStdFn.apply(x, group_size, int(num_channels))
+    return _mbstd_impl(x, group_size, int(num_channels))[0]
+
+
+def mbstd_backward(x, sd, gy, G, F):
+    """p3d_mbstd_backward_f32: the statistic channels' contribution to the gradient of x [N,C,H,W]; gy [N,C+F,H,W] is the cotangent of
+    the concatenated tensor (its last F channels are read in place), sd the forward's deviation map."""
+    x, sd, gy = _chk(x, "x"), _chk(sd, "sd"), _chk(gy, "gy")
+    N, Cc, H, W = x.shape
+    gx = torch.empty_like(x)
+    with _on(x.device):
+        rc = _lib.lib().p3d_mbstd_backward_f32(_p(x), _p(sd), C.c_void_p(gy.data_ptr() + 4 * Cc * H * W), (Cc + F) * H * W, N, Cc, H * W,
+                                               int(G), int(F), _p(gx), _stream())
+    _lib.check(rc, "p3d_mbstd_backward_f32")
+    return gx
+
+
+class _MbStdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, group, F):
+        y, sd, G = _mbstd_impl(x, group, F)
+        ctx.save_for_backward(x, sd)
+        ctx.G, ctx.F = G, F
+        return y
+
+    @staticmethod
+    @_first_order
+    def backward(ctx, gy):
+        x, sd = ctx.saved_tensors
+        gy = gy.contiguous()
+        return mbstd_backward(x, sd, gy, ctx.G, ctx.F).add_(gy[:, :x.shape[1]]), None, None
