@@ -518,6 +518,8 @@ def paste_front(weights, xyz, occ, rays_o, rays_d, front, image, thresh_weight, 
     dict(image, paste, mask, mask_weights, mask_edges, mask_occ, mask_dxyz) at S x S."""
     weights, xyz, occ = _chk(weights, "weights"), _chk(xyz, "xyz"), _chk(occ, "occ")
     rays_o, rays_d, front, image = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(front, "front"), _chk(image, "image")
+    if xyz.dim() != 4 or xyz.shape[1] != 3:  # (the kernel reads three channels of r x r whatever the tensor holds)
+        raise RuntimeError("paste_front: xyz must be [N,3,r,r]")
     N, _, r, r2 = xyz.shape
     S = image.shape[-1]
     if (r != r2 or tuple(weights.shape) != (N, 1, r, r) or tuple(occ.shape) != (N, 1, r, r) or tuple(rays_o.shape) != (N, 3, r, r)

@@ -223,6 +223,35 @@ def test_paste_front_fused_kernel_vs_torch_formulation(hip):
         # the illustration is white noise (gradient ~1 per texel) sampled at coordinates near 512, whose fp32 spacing is 6e-5
         assert float((fused["paste"] - ref["paste"]).abs().max()) < 2e-4 and float((fused["paste"] - ref["paste"]).abs().mean()) < 1e-5
         assert float(((fused["image"] - ref["image"]).abs() * same).max()) < 2e-4
+    # three views of one subject in one call, one shared [1, 3, 512, 512] illustration: `front_shared` and the per-view strides of the
+    # rays, the occlusion render and the maps, under the same gates (one ws for every view, as
+    # test_f_many_views_of_one_subject_in_one_call obtains it: this fixture's generator is pose-conditioned)
+    V, res, S = 3, 16, 12
+    R = res * res
+    draws = [(torch.rand(V, R, S, 1, generator=gen).cuda(), torch.rand(V * R, S, generator=gen).cuda()) for _ in range(2)]
+    x = dict(seeds=[3], cond={"image_ortho_front": front}, triplane_crop=0.1, cull_clouds=0.5, neural_rendering_resolution=res, noise_mode="const")
+    with torch.no_grad():
+        x0 = dict(x, elevations=torch.tensor([0.0]).cuda(), azimuths=torch.tensor([0.0]).cuda(), fovs=torch.tensor([-1.0]).cuda())
+        G._inject_draws = None
+        G.f(x0)
+        x = dict(x, ws=x0["ws"], elevations=torch.tensor([0.0, 10.0, -5.0]).cuda(), azimuths=torch.tensor([0.0, 40.0, 200.0]).cuda(),
+                 fovs=torch.tensor([-1.0, 30.0, 30.0]).cuda(), paste_params=pp)
+        G._inject_draws = [tuple(d) for d in draws]
+        out = G.f(x)
+        ret = {k: out[k] for k in ("image_raw", "image_depth", "image_weights", "triplane", "image_xyz", "normalize_images")}
+        ret["image"] = out["image_prepaste"]
+        G._inject_draws = [tuple(draws[1])]
+        ref = paste.paste_front_torch(G, x, ret, **pp)
+    fused = out["paste"]
+    assert fused["mask"].shape == (V, 1, 512, 512) and ref["paste"].shape == (V, 3, 512, 512)
+    print("pasted share per view:", [round(float(ref["mask"][v].mean()), 4) for v in range(V)])
+    assert 0.005 < float(ref["mask"].mean()) < 0.995
+    for k in ("mask", "mask_weights", "mask_edges", "mask_occ", "mask_dxyz"):
+        assert fused[k].shape == ref[k].shape
+        assert float(((fused[k] - ref[k]).abs() > 1e-4).float().mean()) < 1e-3, k
+    same = (fused["mask"] - ref["mask"]).abs() <= 1e-4
+    assert float((fused["paste"] - ref["paste"]).abs().max()) < 2e-4 and float((fused["paste"] - ref["paste"]).abs().mean()) < 1e-5
+    assert float(((fused["image"] - ref["image"]).abs() * same).max()) < 2e-4
     G._inject_draws = None
 
 
