@@ -364,7 +364,8 @@ int p3d_torgb_f32(const float* x, int N, int I, int H, int W, const float* w_t, 
 
 /* upfirdn2d (torch_utils/ops/upfirdn2d.py:120-167; plugin signature upfirdn2d.cpp:20): zero-insert by `up`, pad/crop,
  * correlate with f [fh][fw] (pass the filter already flipped for convolution and multiplied by the gain), decimate by
- * `down`.  x [NC][H][W] -> y [NC][(H*up+pady0+pady1-fh)/down+1][(W*up+padx0+padx1-fw)/down+1]. */
+ * `down`.  x [NC][H][W] -> y [NC][floor((H*up+pady0+pady1-fh)/down)+1][floor((W*up+padx0+padx1-fw)/down)+1]; a padded, zero-inserted
+ * input smaller than the filter in y or in x (H*up+pady0+pady1 < fh, or the same in x) has no output: P3D_E_RANGE, whatever `down` is. */
 int p3d_upfirdn2d_f32(const float* x, int64_t NC, int H, int W, const float* f, int fh, int fw, int up, int down, int padx0,
                       int padx1, int pady0, int pady1, float* y, void* stream);
 

@@ -584,9 +584,12 @@ int p3d_upfirdn2d_f32(const float* x, int64_t NC, int H, int W, const float* f, 
     FirParams q;
     q.x = x; q.f = f; q.y = y; q.dcoef = nullptr; q.noise = nullptr; q.bias = nullptr;
     q.NC = NC; q.C = 1; q.H = H; q.W = W;
-    q.OH = (H * up + pady0 + pady1 - fh) / down + 1;
-    q.OW = (W * up + padx0 + padx1 - fw) / down + 1;
-    if (q.OH <= 0 || q.OW <= 0) return P3D_E_RANGE;
+    // floor((padded extent - filter) / down) + 1 outputs: a padded, zero-inserted input smaller than the filter has none, whatever down is
+    // (C++ division truncates toward zero: -1 / 2 + 1 would be one output)
+    const long long ey = (long long)H * up + pady0 + pady1 - fh, ex = (long long)W * up + padx0 + padx1 - fw;
+    if (ey < 0 || ex < 0) return P3D_E_RANGE;
+    q.OH = (int)(ey / down) + 1;
+    q.OW = (int)(ex / down) + 1;
     q.fh = fh; q.fw = fw; q.up = up; q.down = down; q.padx0 = padx0; q.pady0 = pady0;
     q.noise_per_sample = 0; q.act = 0; q.epilogue = 0; q.alpha = 0; q.gain = 1; q.clamp = -1; q.ksplit = 1; q.slice = 0; q.nstyles = nullptr; q.pitch = W; q.xoff = 0;
     long long total = q.NC * q.OH * q.OW;

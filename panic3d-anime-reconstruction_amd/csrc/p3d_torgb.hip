@@ -2,6 +2,7 @@
 // as a GEMM that reads its activation once (k_torgb), fused with SynthesisBlock's skip connection (:476-478), and the second half of
 // a ToRGB layer whose channel sums came out of conv1's epilogue (k_torgb_combine; k_modconv_w3<true>, p3d_conv_plain.hip).
 #include "p3d_conv_common.hpp"
+#include "p3d_torgb_plan.hpp"
 #define chk chk_launch
 
 // =====================================================================================================================
@@ -32,7 +33,6 @@ struct TorgbParams {
     int N, I, O, H, W;
     float clamp;
 };
-#define TG_KC 64
 // MS (KS only, MT = 1): the workgroup multiplies ONE of the three 32-channel tiles of a 96-channel layer (blockIdx.z): on the
 // 4^2 .. 64^2 maps a launch is a handful of workgroups, each a serial chain of 192 f32 MFMAs per wave (64 clocks each) — three times
 // the workgroups, a third of the chain; the same sums in the same order.
@@ -280,27 +280,27 @@ int p3d_torgb_weights_f32(const float* w, int O, int I, float* w_t, void* stream
 
 int p3d_torgb_f32(const float* x, int N, int I, int H, int W, const float* w_t, int O, const float* styles, const float* bias, float clamp,
                   const float* skip, const float* skip_fir, float* y, void* stream) {
-    if (!x || !w_t || !styles || !y || N <= 0 || I <= 0 || O <= 0 || H <= 0 || W <= 0) return P3D_E_ARG;
+    if (!x || !w_t || !styles || !y) return P3D_E_ARG;
+    const TorgbPlan pl = p3d_torgb_plan(N, I, O, H, W);  // the instantiation, the grid and the dynamic LDS: p3d_torgb_plan.hpp
+    if (pl.err == P3D_E_ARG) return P3D_E_ARG;
     if ((skip != nullptr) != (skip_fir != nullptr)) return P3D_E_ARG;
-    if (O > 96 || I > 1024 || (long long)I * H * W * 4 >= (1ll << 31) || (skip && ((H & 1) || (W & 1)))) return P3D_E_RANGE;
+    if (pl.err) return pl.err;
+    if (skip && ((H & 1) || (W & 1))) return P3D_E_RANGE;
     TorgbParams p;
     p.x = x; p.wt = w_t; p.styles = styles; p.bias = bias; p.skip = skip; p.skipf = skip_fir; p.y = y;
     p.N = N; p.I = I; p.O = O; p.H = H; p.W = W; p.clamp = clamp;
-    const int HW = H * W, MT = O <= 32 ? 1 : 3;
-    // PX shape (a wave = 32 pixels x all K) once the map alone gives >= 512 workgroups of 128 pixels; KS (a workgroup = 32 pixels,
-    // waves split K) below that
-    const bool ks = (long long)N * ((HW + 127) / 128) < 512;
-    // small maps of a 96-channel layer: one workgroup per 32-channel tile while that still leaves the chip underfilled
-    const bool ms = ks && MT == 3 && (long long)N * ((HW + 31) / 32) * 3 <= 1024;
-    const bool pre = ms && I <= 8 * TG_KC;  // everything requested up front (k_torgb<..., PRE>)
-    const size_t lds = (size_t)(2 * TG_KC * 32 * (ms ? 1 : MT) + (pre ? 8 * TG_KC : ((I + 63) / 64) * 64)) * 4;
-    dim3 grid((unsigned)(ks ? (HW + 31) / 32 : (HW + 127) / 128), (unsigned)N, ms ? 3u : 1u);
-    if (lds > 64 * 1024) return P3D_E_RANGE;  // (53 KB at I = 1024, O = 96: inside the default dynamic-LDS limit, no per-device attribute to set)
-#define P3D_TORGB(MTV, KSV) hipLaunchKernelGGL((k_torgb<MTV, KSV>), grid, dim3(256), lds, (hipStream_t)stream, p)
-    if (MT == 1) { if (ks) P3D_TORGB(1, true); else P3D_TORGB(1, false); }
-    else if (pre) hipLaunchKernelGGL((k_torgb<1, true, true, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
-    else if (ms) hipLaunchKernelGGL((k_torgb<1, true, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
-    else { if (ks) P3D_TORGB(3, true); else P3D_TORGB(3, false); }
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    const size_t lds = pl.lds_bytes;
+#define P3D_TORGB(...) hipLaunchKernelGGL((k_torgb<__VA_ARGS__>), grid, dim3(256), lds, (hipStream_t)stream, p)
+    switch (pl.kernel) {
+    case TorgbKernel::PX1: P3D_TORGB(1, false); break;
+    case TorgbKernel::KS1: P3D_TORGB(1, true); break;
+    case TorgbKernel::PX3: P3D_TORGB(3, false); break;
+    case TorgbKernel::KS3: P3D_TORGB(3, true); break;
+    case TorgbKernel::MS: P3D_TORGB(1, true, true); break;
+    case TorgbKernel::MS_PRE: P3D_TORGB(1, true, true, true); break;
+    }
+#undef P3D_TORGB
     return chk();
 }
 

@@ -741,6 +741,9 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
     ff = prepared_filter(f, x.device, gain, flip_filter)
     N, Cc, H, W = x.shape
     fh, fw = ff.shape
+    if H * up + py0 + py1 < fh or W * up + px0 + px1 < fw:
+        raise RuntimeError(f"upfirdn2d: the padded input ({H * up + py0 + py1} x {W * up + px0 + px1}) is smaller than the "
+                           f"{fh} x {fw} filter: no output")
     OH = (H * up + py0 + py1 - fh) // down + 1
     OW = (W * up + px0 + px1 - fw) // down + 1
     y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=x.device)
@@ -770,14 +773,16 @@ def upsample2d_add(x, f, add=None):
     (networks_stylegan2.py:476-478): returns upsample2d(x, f) + add in one launch (polyphase FIR, same bits as upfirdn2d)."""
     x = _chk(x, "x")
     N, Cc, H, W = x.shape
-    if tuple(f.shape) != (4, 4) or (2 * W) % 4 != 0:
-        y = upsample2d(x, f)
-        return y if add is None else y.add_(add)
-    ff = prepared_filter(f, x.device, 4.0, False)
     if add is not None:
         add = _chk(add, "add")
         if tuple(add.shape) != (N, Cc, 2 * H, 2 * W):
             raise RuntimeError("add must be [N,C,2H,2W]")
+    # the fused kernel moves float4 rows: a 2W that is no multiple of 4, or an `add` that is not 16-byte aligned (a contiguous view at
+    # a storage offset), takes the generic operator (the library's P3D_E_RANGE says the same)
+    if tuple(f.shape) != (4, 4) or (2 * W) % 4 != 0 or (add is not None and add.data_ptr() % 16 != 0):
+        y = upsample2d(x, f)
+        return y if add is None else y.add_(add)
+    ff = prepared_filter(f, x.device, 4.0, False)
     y = torch.empty((N, Cc, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
     with _on(x.device):
         rc = _lib.lib().p3d_upsample2d_add_f32(_p(x), N * Cc, H, W, _p(ff), _p(add), _p(y), _stream())

@@ -95,17 +95,31 @@ def test_filtered_resizing(P, monkeypatch, mode):
 
 
 def test_fir_adjoint_of_the_down_sampling_layers(P, monkeypatch):
-    """ops.fir's backward (ops._upfirdn2d_adjoint) for the two FIR calls of a down-sampling layer, against autograd of the stand-in."""
+    """ops.fir's backward (ops._upfirdn2d_adjoint) against autograd: first the two FIR calls of a down-sampling layer at 8 x 8, on
+    seeded draws, against binary32 autograd of the stand-in; then every case of tests/resample_cases.py — asymmetric and non-square
+    filters, odd sizes, up and down together, unequal and negative padding, flip_filter — on the case's own inputs against float64
+    autograd under the project's gate (its scale is the sum of the |terms|, so a one-element gradient whose terms cancel is judged by
+    what binary32 can deliver, which a relative L2 bound is not)."""
+    import resample_cases as RC
+    from synthesis_grad_ref import gate
     DC.install_ops(monkeypatch, P.ops)
     f = P.ops.setup_filter([1, 3, 3, 1])
+    gen = torch.Generator().manual_seed(4)
     for kw in (dict(padding=[2, 2, 2, 2]), dict(down=2, padding=[1, 1, 1, 1])):
-        x = torch.randn(2, 3, 8, 8, requires_grad=True)
+        x = torch.randn(2, 3, 8, 8, generator=gen, requires_grad=True)
         y = P.ops.fir(x, f, **kw)
-        g = torch.randn_like(y)
+        g = torch.randn(y.shape, generator=gen)
         y.backward(g)
         x2 = x.detach().clone().requires_grad_(True)
         DC.upfirdn2d_torch(x2, f, **kw).backward(g)
         assert DC.rel_l2(x.grad, x2.grad) < 1e-6, kw
+    for c in RC.CASES:
+        x, fc, g = RC.make_inputs(c)
+        ref = RC.case_ref(c)
+        xg = x.clone().requires_grad_(True)
+        P.ops.fir(xg, fc, **RC.kwargs(c)).backward(g)
+        assert xg.grad.shape == ref["gx"].shape, c.id
+        gate(f"{c.id} ops.fir backward", xg.grad, ref["gx"], ref["gx_absref"], ref["K"])
 
 
 # ---- the layer gates and their sensitivity --------------------------------------------------------------------------------------------
