@@ -20,7 +20,7 @@
 
 #define P3D_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0)
 
-// ---- tolerance mode of the FINAL pass (P3D_FLAG_FAST_COLOR; DESIGN.md §4.6) --------------------------------------------
+// ---- tolerance mode of the FINAL pass (P3D_FLAG_FAST_COLOR; DESIGN.md §4.5) --------------------------------------------
 // Both layers on v_mfma_f32_32x32x16_f16 (16x the f32 MFMA rate) with every operand split into two f16 terms
 // (x = xh + xl, xh = f16(x) by truncation, xl = f16(x - xh)): x*w ~ xh*wh + xl*wh + xh*wl, fp32 accumulation — about 2^-21
 // relative per product — and the activations on the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32).
@@ -609,8 +609,14 @@ P3D_DEV float p3d_sigmoid_hw(float x) {
 // (surface scene: 0.4 % of the final steps).  With it the tolerance mode makes the SAME mask decisions as the exact contract
 // (as long as the tolerance decoder's own error in the opacity stays below the band: |sigma error| < 8e-3, i.e. sigma-row
 // products up to ~10^4), and its outputs differ from the exact ones by arithmetic round-off only: a stated, asserted bound
-// (DESIGN.md §4.6) instead of "a few rays flip".
+// (DESIGN.md §4.5) instead of "a few rays flip".
 #define P3D_FAST_MASK_BAND 2e-3f
+// TERMINATION (the renderers' final pass with the early-outs): a ray is dropped once its transmittance Td is below P3D_FAST_TD_CUT.
+// The weights it would still have added sum to r <= Td, so the cut leaves r out of wsum, at most 2 r |c - b| <= 2 r out of a colour
+// and 2 r |p - b| out of xyz (outputs are 2 (sum w v + b (1 - W)) - 1 with b = 1 on a white background, else 0; c in [0, 1], p the
+// sample position): 1e-6 (|p| + 1) per coordinate at most.  The xyz bound of 1e-5 is stated for positions within
+// 4 per coordinate, where the cut takes at most half of it and round-off (2 |p| times the error of the weights) the rest.
+#define P3D_FAST_TD_CUT 5e-7
 template <bool WANT_RGB, bool LAZY = false, bool GUARD = false>
 P3D_DEV bool p3d_decode_features_fast(const float* lds, const P3dDecodeCfg& cfg, const f32x16& X, float px, float pz, float& sigma_out,
                                       f32x16& rgb, bool live = true);

@@ -643,9 +643,11 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 advance(take_c);
             } else {
                 // exact mode: below 1e-60 every later weight alpha * (float)Td is exactly 0.  Tolerance mode: the transmittance
-                // bounds everything the rest of the ray can still add (sum of the remaining weights <= Td): stop at 2e-6,
-                // i.e. <= 4e-6 on a colour, <= 6e-6 on depth / weight sum — early ray termination, inside the 2e-5 budget
-                if (!done && st.Td < (FAST ? 2e-6 : 1e-60)) done = true;
+                // bounds everything the rest of the ray can still add (sum of the remaining weights <= Td): stop at P3D_FAST_TD_CUT,
+                // (what that leaves out of each output: p3d_decode.hpp) — early ray termination, inside the stated bound
+                // ... and a ray that has taken its last sample is done whatever that sample was: the jump below, which also notices
+                // the end of the list, is not reached behind a sigma > 602 (binarize's solid value as the LAST sample)
+                if (!done && (m >= S || st.Td < (FAST ? P3D_FAST_TD_CUT : 1e-60))) done = true;
                 if (!done && (first || st.prev_sigma <= 602.0f)) {
                     // jump over the run of known samples that starts at m (one iteration per 32-bit word the run touches)
                     bool any = false, last_c = false;
@@ -770,7 +772,7 @@ P3D_DEV float p3d_select(const float (&x)[N], int k) {
 // moves per step with four slots instead of 48 + 192 selects).  Then every lane consumes the step's samples in order.
 // Bit-identical to k_render.  No dumps on this path (the host falls back to k_render for them).
 // FAST (P3D_FLAG_FAST_COLOR): the final pass decodes in tolerance mode exactly as k_render<…, FAST = true> does (two-term f16 MLP
-// operands, hardware transcendentals, the exact mask guard, rays dropped below a transmittance of 2e-6); the coarse pass, and
+// operands, hardware transcendentals, the exact mask guard, rays dropped below a transmittance of P3D_FAST_TD_CUT); the coarse pass, and
 // with it every importance draw, stays on the exact contract.
 // WO ("weights only", P3D_FLAG_WEIGHTS_ONLY; four-slot tolerance-mode instantiations only): the launch is asked for the accumulated
 // opacity (wsum) and depth alone — the occlusion pass of paste_front (training/triplane.py:565-578 reads `image_weights` of a second
@@ -955,8 +957,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_slots_occ(SLOTS, 
             bool skipped = false, live = true;
             if (early) {
                 // exact mode: below 1e-60 every later weight is exactly 0.  Tolerance mode: the transmittance bounds what the rest
-                // of the ray can still add — stop at 2e-6, inside the 2e-5 budget (as in k_render)
-                live = !(cx.cropped(px, pz) || st.Td < (FAST ? 2e-6 : 1e-60));
+                // of the ray can still add — stop at P3D_FAST_TD_CUT (p3d_decode.hpp, as in k_render)
+                live = !(cx.cropped(px, pz) || st.Td < (FAST ? P3D_FAST_TD_CUT : 1e-60));
                 skipped = __builtin_amdgcn_ballot_w64(live) == 0;
             }
             if (!skipped) {

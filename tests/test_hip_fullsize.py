@@ -142,7 +142,7 @@ def test_large_launch_other_sampling_rates(hip, oracle, Sc, Sf):
         assert float(err.median()) <= 2e-6 and float(err.max()) <= FAST_MAX[name], (name, float(err.max()))  # every ray
 
 
-FAST_MAX = dict(feat=1e-5, depth=2e-5, wsum=1e-5, xyz=1e-5)  # the tolerance mode's stated bound vs the exact contract (DESIGN.md §4.6)
+FAST_MAX = dict(feat=1e-5, depth=2e-5, wsum=1e-5, xyz=1e-5)  # the tolerance mode's stated bound vs the exact contract (DESIGN.md §4.5)
 
 
 # ---- full-size holes closed in round 2 (VERDICT r01 "What's weak" 1-2) ---------------------------------------------------

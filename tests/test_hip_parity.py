@@ -463,7 +463,7 @@ def _psnr(a, b):
     return np.inf if mse == 0 else 10 * np.log10(1.0 / mse)
 
 
-# the stated bound of the tolerance mode against the exact contract (DESIGN.md §4.6, INTEGRATION.md), every ray, every output
+# the stated bound of the tolerance mode against the exact contract (DESIGN.md §4.5, INTEGRATION.md), every ray, every output
 FAST_MAX = dict(feat=1e-5, depth=2e-5, wsum=1e-5, xyz=1e-5)
 
 
@@ -508,7 +508,7 @@ def test_fast_color_keeps_the_coarse_pass_exact_and_the_outputs_close(hip, oracl
             assert np.median(err) <= 2e-6 and err.max() <= FAST_MAX[nm], (small, nm, float(err.max()), int((err > FAST_MAX[nm]).sum()))
     # HARD bound (round 3): the exact mask guard (p3d_decode.hpp, P3D_FAST_MASK_BAND) makes the tolerance mode take the same
     # crop / cull decisions as the exact contract, so what is left is arithmetic round-off (two-term f16 products, hardware
-    # exp2 / log2 / rcp, ray termination at Td < 2e-6): EVERY ray within FAST_MAX of the oracle, no allowance for flipped rays.
+    # exp2 / log2 / rcp, ray termination at Td < P3D_FAST_TD_CUT): EVERY ray within FAST_MAX of the oracle, no allowance for flipped rays.
     for nm, a, b in zip(("feat", "depth", "wsum", "xyz"), prod, ref[:4]):
         a = a.cpu().numpy()
         err = np.abs(a - b).reshape(R, -1).max(axis=1)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""P3D_FLAG_FAST_COLOR vs the exact contract on the GPU: error statistics and kernel time (DESIGN.md §4.6).
+"""P3D_FLAG_FAST_COLOR vs the exact contract on the GPU: error statistics and kernel time (DESIGN.md §4.5).
     python tools/fast_color_check.py [--res 512]"""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
