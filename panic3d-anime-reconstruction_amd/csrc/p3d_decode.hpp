@@ -174,6 +174,30 @@ template <int CTRL>  // quad_perm: lane i of every quad reads lane (CTRL >> 2i) 
 P3D_DEV uint32_t p3d_quad_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true); }
 template <int CTRL>
 P3D_DEV float p3d_quad_f(float v) { return __builtin_bit_cast(float, p3d_quad_u<CTRL>(__builtin_bit_cast(uint32_t, v))); }
+// P3D_QUAD_EXCHANGE = 1 (shipped): the quad-cooperative gather moves its data between lanes inside the instructions that use it —
+// the bilinear weight of ray r is the DPP operand of the fma that takes it (p3d_fmac_quad16) and the quad transpose is a two-stage
+// exchange of v_cndmask_b32_dpp (p3d_quad_transpose).  0: the former route — one v_mov_b32_dpp per weight and tap, and a transpose
+// by row rotation (80 selects + 12 moves) — kept for A/B runs.  The same operations on the same operands either way: same bits.
+#ifndef P3D_QUAD_EXCHANGE
+#define P3D_QUAD_EXCHANGE 1
+#endif
+// f[c] = fma(w of lane (c >> 2) of the quad, v[c], f[c]) for the 16 registers of one tap: v_fmac_f32 (the fused multiply-add the
+// compiler emits for p3d_fma here) with the weight as its DPP source.  The compiler pads no hazard inside an asm statement: a
+// VALU write of w needs two wait states before a DPP read of it, hence the s_nop that opens each half.  All lanes active.
+#define P3D_FMAC_Q(F, V, R) "v_fmac_f32_dpp %" #F ", %16, %" #V " quad_perm:[" #R "," #R "," #R "," #R "] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+P3D_DEV void p3d_fmac_quad16(f32x16& f, float w, const f32x16& v) {
+    asm("s_nop 1\n\t"
+        P3D_FMAC_Q(0, 8, 0) P3D_FMAC_Q(1, 9, 0) P3D_FMAC_Q(2, 10, 0) P3D_FMAC_Q(3, 11, 0)
+        P3D_FMAC_Q(4, 12, 1) P3D_FMAC_Q(5, 13, 1) P3D_FMAC_Q(6, 14, 1) P3D_FMAC_Q(7, 15, 1)
+        : "+v"(f.s0), "+v"(f.s1), "+v"(f.s2), "+v"(f.s3), "+v"(f.s4), "+v"(f.s5), "+v"(f.s6), "+v"(f.s7)
+        : "v"(v.s0), "v"(v.s1), "v"(v.s2), "v"(v.s3), "v"(v.s4), "v"(v.s5), "v"(v.s6), "v"(v.s7), "v"(w));
+    asm("s_nop 1\n\t"
+        P3D_FMAC_Q(0, 8, 2) P3D_FMAC_Q(1, 9, 2) P3D_FMAC_Q(2, 10, 2) P3D_FMAC_Q(3, 11, 2)
+        P3D_FMAC_Q(4, 12, 3) P3D_FMAC_Q(5, 13, 3) P3D_FMAC_Q(6, 14, 3) P3D_FMAC_Q(7, 15, 3)
+        : "+v"(f.s8), "+v"(f.s9), "+v"(f.sa), "+v"(f.sb), "+v"(f.sc), "+v"(f.sd), "+v"(f.se), "+v"(f.sf)
+        : "v"(v.s8), "v"(v.s9), "v"(v.sa), "v"(v.sb), "v"(v.sc), "v"(v.sd), "v"(v.se), "v"(v.sf), "v"(w));
+}
+#undef P3D_FMAC_Q
 // QUAD: the registers of a tap are [ray of the quad][4 channels] (p3d_load16_quad), so register c takes the weight of ray c >> 2.
 template <bool QUAD = false, typename LOAD>
 P3D_DEV f32x16 p3d_fold_taps(const float wg[12], LOAD load) {
@@ -185,18 +209,22 @@ P3D_DEV f32x16 p3d_fold_taps(const float wg[12], LOAD load) {
     for (int k = 0; k < 12; ++k) {
         __builtin_amdgcn_sched_barrier(0);
         const f32x16 v = tap[k % P3D_GATHER_DEPTH];
-        float w4[4];
-        if constexpr (QUAD) {
-            w4[0] = p3d_quad_f<0x00>(wg[k]); w4[1] = p3d_quad_f<0x55>(wg[k]); w4[2] = p3d_quad_f<0xaa>(wg[k]); w4[3] = p3d_quad_f<0xff>(wg[k]);
+        if (QUAD && P3D_QUAD_EXCHANGE && (k & 3) != 0) {
+            p3d_fmac_quad16(f, wg[k], v);
         } else {
-            w4[0] = w4[1] = w4[2] = w4[3] = wg[k];
-        }
-        if ((k & 3) == 0) {
+            float w4[4];
+            if constexpr (QUAD) {  // (a multiply takes the moved weight as its DPP operand by itself: v_mul_f32_dpp)
+                w4[0] = p3d_quad_f<0x00>(wg[k]); w4[1] = p3d_quad_f<0x55>(wg[k]); w4[2] = p3d_quad_f<0xaa>(wg[k]); w4[3] = p3d_quad_f<0xff>(wg[k]);
+            } else {
+                w4[0] = w4[1] = w4[2] = w4[3] = wg[k];
+            }
+            if ((k & 3) == 0) {
 #pragma unroll
-            for (int c = 0; c < 16; ++c) f[c] = w4[c >> 2] * v[c];
-        } else {
+                for (int c = 0; c < 16; ++c) f[c] = w4[c >> 2] * v[c];
+            } else {
 #pragma unroll
-            for (int c = 0; c < 16; ++c) f[c] = p3d_fma(w4[c >> 2], v[c], f[c]);
+                for (int c = 0; c < 16; ++c) f[c] = p3d_fma(w4[c >> 2], v[c], f[c]);
+            }
         }
         // pin the partial sums here: without it the compiler sinks all the arithmetic below the last load (sched_barrier only
         // orders machine instructions that already sit on either side of it) and every tap stays live.  At the end of a plane the
@@ -251,6 +279,60 @@ P3D_DEV f32x16 p3d_load16_quad(RSRC rs, uint32_t off) {
 }
 
 // in: [4 r + d] = channels 4 i + d of sample r (lane i of the quad); out: [4 p + d] = channels 4 p + d of this lane's sample.
+#if P3D_QUAD_EXCHANGE
+// Per d a 4 x 4 transpose between the lanes of the quad and the rows r, as a two-stage exchange: stage 1 swaps bit 0 of the lane
+// with bit 0 of the row (partner lane i ^ 1, row pairs (0,1) and (2,3)), stage 2 bit 1 with bit 1 (partner i ^ 2, row pairs (0,2)
+// and (1,3)).  For a row pair (A, B) a lane whose bit is clear keeps A and takes the partner's A as its B; a lane whose bit is set
+// takes the partner's B as its A and keeps B:
+//     A' = clear ? A : B of the partner      B' = set ? B : A of the partner
+// each ONE v_cndmask_b32_dpp (D = vcc ? src1 : src0, the partner's register as the DPP source src0, the lane-parity mask — a
+// constant — in VCC): 32 instructions for the 16 registers.  B' is written in place (A is still whole), A' into a register that is
+// free: eight temporaries in stage 1, the dead A registers of stage 1 in stage 2.  (Four temporaries and twice the VCC set-ups
+// allocate the same registers in every render kernel: the temporaries are not what bounds them.)
+// Wait states the compiler does not pad inside an asm statement: a VALU write -> a DPP read of that register needs two, so the
+// statement opens with s_nop 1 (its inputs come straight from the fold), stage 1 writes rows 3 before rows 1 and stage 2 reads rows
+// 2 before rows 3 (>= 6 instructions between any write and its DPP read); it closes with s_nop 1 because its outputs are MFMA
+// operands (VALU write -> MFMA read: two).  All 64 lanes active.
+//   operands: %0-%15 = x[4 r + d], %16-%23 = t[0..7]
+#define P3D_QSEL(D, OWN, PARTNER, PERM) "v_cndmask_b32_dpp %" #D ", %" #PARTNER ", %" #OWN ", vcc quad_perm:" PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define P3D_QMASK(M) "s_mov_b32 vcc_lo, " M "\n\ts_mov_b32 vcc_hi, " M "\n\t"
+#define P3D_X1 "[1,0,3,2]"
+#define P3D_X2 "[2,3,0,1]"
+P3D_DEV f32x16 p3d_quad_transpose(const f32x16& in) {
+    f32x16 x = in;
+    float t0, t1, t2, t3, t4, t5, t6, t7;
+    asm("s_nop 1\n\t"
+        // stage 1, A' of rows (0,1) -> t[d], of rows (2,3) -> t[4 + d]: lanes 0, 2 keep A
+        P3D_QMASK("0x55555555")
+        P3D_QSEL(16, 0, 4, P3D_X1) P3D_QSEL(17, 1, 5, P3D_X1) P3D_QSEL(18, 2, 6, P3D_X1) P3D_QSEL(19, 3, 7, P3D_X1)
+        P3D_QSEL(20, 8, 12, P3D_X1) P3D_QSEL(21, 9, 13, P3D_X1) P3D_QSEL(22, 10, 14, P3D_X1) P3D_QSEL(23, 11, 15, P3D_X1)
+        // stage 1, B' in place (rows 3, then rows 1): lanes 1, 3 keep B
+        P3D_QMASK("0xaaaaaaaa")
+        P3D_QSEL(12, 12, 8, P3D_X1) P3D_QSEL(13, 13, 9, P3D_X1) P3D_QSEL(14, 14, 10, P3D_X1) P3D_QSEL(15, 15, 11, P3D_X1)
+        P3D_QSEL(4, 4, 0, P3D_X1) P3D_QSEL(5, 5, 1, P3D_X1) P3D_QSEL(6, 6, 2, P3D_X1) P3D_QSEL(7, 7, 3, P3D_X1)
+        // now row 0 = t[d], row 1 = x[4 + d], row 2 = t[4 + d], row 3 = x[12 + d]; x[d] and x[8 + d] are free
+        // stage 2, A' of rows (0,2) -> x[d], of rows (1,3) -> x[8 + d]: lanes 0, 1 keep A
+        P3D_QMASK("0x33333333")
+        P3D_QSEL(0, 16, 20, P3D_X2) P3D_QSEL(1, 17, 21, P3D_X2) P3D_QSEL(2, 18, 22, P3D_X2) P3D_QSEL(3, 19, 23, P3D_X2)
+        P3D_QSEL(8, 4, 12, P3D_X2) P3D_QSEL(9, 5, 13, P3D_X2) P3D_QSEL(10, 6, 14, P3D_X2) P3D_QSEL(11, 7, 15, P3D_X2)
+        // stage 2, B' in place: lanes 2, 3 keep B
+        P3D_QMASK("0xcccccccc")
+        P3D_QSEL(20, 20, 16, P3D_X2) P3D_QSEL(21, 21, 17, P3D_X2) P3D_QSEL(22, 22, 18, P3D_X2) P3D_QSEL(23, 23, 19, P3D_X2)
+        P3D_QSEL(12, 12, 4, P3D_X2) P3D_QSEL(13, 13, 5, P3D_X2) P3D_QSEL(14, 14, 6, P3D_X2) P3D_QSEL(15, 15, 7, P3D_X2)
+        "s_nop 1"
+        : "+v"(x.s0), "+v"(x.s1), "+v"(x.s2), "+v"(x.s3), "+v"(x.s4), "+v"(x.s5), "+v"(x.s6), "+v"(x.s7), "+v"(x.s8), "+v"(x.s9),
+          "+v"(x.sa), "+v"(x.sb), "+v"(x.sc), "+v"(x.sd), "+v"(x.se), "+v"(x.sf),
+          "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(t4), "=&v"(t5), "=&v"(t6), "=&v"(t7)
+        :
+        : "vcc");
+    // row 0 = x[d], row 1 = x[8 + d], row 2 = t[4 + d], row 3 = x[12 + d]
+    return (f32x16){x.s0, x.s1, x.s2, x.s3, x.s8, x.s9, x.sa, x.sb, t4, t5, t6, t7, x.sc, x.sd, x.se, x.sf};
+}
+#undef P3D_QSEL
+#undef P3D_QMASK
+#undef P3D_X1
+#undef P3D_X2
+#else
 // rotate the rows by the lane index, move row q from lane (i - q) & 3 (one DPP each), rotate back.  The lane-dependent
 // selects are written as bit-field inserts under per-lane masks ((m & a) | (~m & b) = one v_bfi / v_bitop3 each): as `?:` on
 // lane predicates the optimiser re-derived them into compare-and-select chains on the lane index — 700 instructions per
@@ -295,6 +377,7 @@ P3D_DEV f32x16 p3d_quad_transpose(const f32x16& in) {
     }
     return out;
 }
+#endif  // P3D_QUAD_EXCHANGE
 
 // This lane's 16 interpolated feature channels (16h .. 16h+15) of the sample at (px,py,pz): the three bilinear plane samples
 // and their mean (renderer.py:68-81, triplane.py:530), gathered straight from the planes (per-lane L1 gathers).
@@ -461,6 +544,17 @@ P3D_DEV f32x16 p3d_gather_features_boxed(const float* box, const P3dBox b[3], co
     return p3d_fold_taps(wg, [&](int k) { return p3d_lds16(box, of[k]); });
 }
 
+// rgb = sigmoid * (1 + 2 * 0.001) - 0.001 unless force_sigmoid (triplane.py:542): the flag is uniform over the launch, so ONE branch
+// on it per decode instead of a multiply, an add and a select per channel.  (The pin keeps the optimiser from turning the branch
+// back into sixteen selects.)
+P3D_DEV void p3d_widen_unless_forced(const P3dDecodeCfg& cfg, f32x16& rgb) {
+    if (!(cfg.flags & P3D_FLAG_FORCE_SIGMOID)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rgb[r] = rgb[r] * 1.002f - 0.001f;
+        p3d_pin16(rgb);
+    }
+}
+
 // masks on raw sigma: renderer.py:138-153,187-198
 P3D_DEV float p3d_apply_masks(const P3dDecodeCfg& cfg, float px, float pz, float sigma) {
     if (cfg.flags & P3D_FLAG_CROP) {
@@ -562,12 +656,9 @@ P3D_DEV bool p3d_decode_features(const float* lds, const P3dDecodeCfg& cfg, cons
 #pragma unroll
             for (int e = 0; e < 4; ++e) o = P3D_MFMA(a[e], acc1[4 * s4 + e], o);
         }
-        const bool fs = (cfg.flags & P3D_FLAG_FORCE_SIGMOID) != 0;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float sg = p3d_sigmoid(o[r]);
-            rgb[r] = fs ? sg : sg * 1.002f - 0.001f;
-        }
+        for (int r = 0; r < 16; ++r) rgb[r] = p3d_sigmoid(o[r]);
+        p3d_widen_unless_forced(cfg, rgb);
     }
     return WANT_RGB;
 }
@@ -714,12 +805,9 @@ P3D_DEV bool p3d_decode_features_fast(const float* lds, const P3dDecodeCfg& cfg,
             o = P3D_MFMA_H(al, hh, o);
             o = P3D_MFMA_H(ah, hh, o);
         }
-        const bool fs = (cfg.flags & P3D_FLAG_FORCE_SIGMOID) != 0;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float sg = p3d_sigmoid_hw(o[r]);
-            rgb[r] = fs ? sg : sg * 1.002f - 0.001f;
-        }
+        for (int r = 0; r < 16; ++r) rgb[r] = p3d_sigmoid_hw(o[r]);
+        p3d_widen_unless_forced(cfg, rgb);
     }
     return WANT_RGB;
 }
