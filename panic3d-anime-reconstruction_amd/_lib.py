@@ -142,7 +142,17 @@ DISC_SIGNATURES = {
     "p3d_mbstd_f32": (_I, [_P, _I, _I, _L, _I, _I, _I, _P, _P, _P]),
     "p3d_mbstd_backward_f32": (_I, [_P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _P]),
 }
-P3D_GRAD_STATS_BYTES = 256  # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
+# symbol -> (restype, argtypes); every function include/p3d_loss.h declares (the training loss's blur, L1 and view terms)
+LOSS_SIGNATURES = {
+    "p3d_blur_f32": (_I, [_P, _L, _I, _I, _P, _I, _P, _P]),
+    "p3d_l1_workspace_bytes": (_Z, [_L]),
+    "p3d_l1_f32": (_I, [_P, _P, _L, _F, _P, _P, _P, _Z, _P]),
+    "p3d_view_terms_workspace_bytes": (_Z, [_I, _I]),
+    "p3d_view_terms_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _Z, _P]),
+}
+P3D_BLUR_MAX_TAPS = 127                                # include/p3d_loss.h
+P3D_DEPTH_Z, P3D_DEPTH_X, P3D_DEPTH_NORM = 0, 1, 2     # include/p3d_loss.h
+P3D_GRAD_STATS_BYTES = 256 # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
 
 _LIB = None
 
@@ -162,7 +172,7 @@ def lib():
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
-                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()):
+                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

@@ -1621,3 +1621,152 @@ class _MbStdFn(torch.autograd.Function):
         x, sd = ctx.saved_tensors
         gy = gy.contiguous()
         return mbstd_backward(x, sd, gy, ctx.G, ctx.F).add_(gy[:, :x.shape[1]]), None, None
+
+
+# ======================================================================================================================
+# The training loss's operators (include/p3d_loss.h)
+# ======================================================================================================================
+BLUR_TILE = (32, 64)  # csrc/p3d_loss.hip: the blur's tile (rows, columns) up to 69 taps; 16 rows above
+
+
+def gaussian_filter(sigma, device=None):
+    """The 1-D filter of the loss's blur, built as loss_orthocondA.py:186 builds it: 2^-((i / sigma)^2) for i = -R .. R, R = floor(3 sigma),
+    normalised to sum 1; None for R = 0."""
+    R = np.floor(sigma * 3)
+    if R <= 0:
+        return None
+    f = torch.arange(-R, R + 1, device=device).div(sigma).square().neg().exp2()
+    return f / f.sum()
+
+
+def _blur_impl(x, f):
+    x, f = _chk(x, "x"), _chk(f, "f")
+    if x.ndim < 2 or f.ndim != 1:
+        raise RuntimeError("blur_fir: x [..., H, W] and a 1-D filter")
+    H, W = x.shape[-2:]
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    with _on(x.device):
+        rc = _lib.lib().p3d_blur_f32(_p(x), x.numel() // (H * W), H, W, _p(f), f.numel(), _p(y), _stream())
+    _lib.check(rc, "p3d_blur_f32")
+    return y
+
+
+class _BlurFn(torch.autograd.Function):
+    """The blur is linear: its backward is the same operator with the flipped filter, called through blur_fir again, so the backward is
+    itself recorded when autograd asks for it (create_graph=True) and the operator is differentiable to any order."""
+
+    @staticmethod
+    def forward(ctx, x, f):
+        ctx.f = f
+        return _blur_impl(x, f)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return blur_fir(gy, ctx.f.flip(0)), None
+
+
+def blur_fir(x, f):
+    """p3d_blur_f32: the separable 'same'-size correlation of x [..., H, W] with the 1-D filter f (odd, at most 127 taps) along both axes,
+    zero boundary.  A plain call under no_grad; differentiable in x to any order under autograd — same forward bits."""
+    if _wants_grad(x):
+        return _BlurFn.apply(x, f.detach())
+    return _blur_impl(x, f)
+
+
+def blur(x, sigma):
+    """The Gaussian blur of run_D and of the raw target (loss_orthocondA.py:182-187, :222-226): upfirdn2d.filter2d(x, f / f.sum()) with the
+    filter of gaussian_filter(sigma); x itself when floor(3 sigma) == 0."""
+    f = gaussian_filter(sigma, x.device)
+    return x if f is None else blur_fir(x, f)
+
+
+def _l1_impl(a, b, scale, want_grad):
+    a, b = _chk(a, "a"), _chk(b, "b")
+    if a.shape != b.shape or a.numel() == 0:
+        raise RuntimeError("l1_mean: a and b must have the same, non-empty shape")
+    n = a.numel()
+    L = _lib.lib()
+    ws = _sg_workspace(a.device, L.p3d_l1_workspace_bytes(n))
+    out = torch.empty((1,), dtype=torch.float32, device=a.device)
+    ga = torch.empty_like(a) if want_grad else None
+    with _on(a.device):
+        rc = L.p3d_l1_f32(_p(a), _p(b), n, float(scale), _p(out), _p(ga), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_l1_f32")
+    return out[0] / n, ga
+
+
+class _L1MeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        y, ga = _l1_impl(a, b, 1.0 / a.numel(), True)
+        ctx.save_for_backward(ga)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        ga, = ctx.saved_tensors
+        ga = ga * g
+        return (ga if ctx.needs_input_grad[0] else None), (-ga if ctx.needs_input_grad[1] else None)
+
+
+def l1_mean(a, b):
+    """(a - b).abs().mean() on p3d_l1_f32.  Under autograd the gradient sign(a - b) / n (sign(0) = 0) is written by the forward launch
+    and multiplied by the incoming cotangent in backward."""
+    if _wants_grad(a, b):
+        return _L1MeanFn.apply(a, b)
+    return _l1_impl(a, b, 0.0, False)[0]
+
+
+DEPTH_MODES = {"z": _lib.P3D_DEPTH_Z, "x": _lib.P3D_DEPTH_X, "norm": _lib.P3D_DEPTH_NORM}
+
+
+def _view_terms_impl(weights, xyz, gt_alpha, gt_xyz, depth_mode, q, want_grad):
+    weights, xyz, gt_alpha, gt_xyz = _chk(weights, "weights"), _chk(xyz, "xyz"), _chk(gt_alpha, "gt_alpha"), _chk(gt_xyz, "gt_xyz")
+    if depth_mode not in DEPTH_MODES:
+        raise RuntimeError(f"view_terms: depth_mode must be one of {sorted(DEPTH_MODES)}")
+    N, r, S = weights.shape[0], weights.shape[-1], gt_alpha.shape[-1]
+    if tuple(weights.shape) != (N, 1, r, r) or tuple(xyz.shape) != (N, 3, r, r) or tuple(gt_alpha.shape) != (N, 1, S, S) \
+            or tuple(gt_xyz.shape) != (N, 3, S, S):
+        raise RuntimeError("view_terms: weights [N,1,r,r], xyz [N,3,r,r], gt_alpha [N,1,S,S], gt_xyz [N,3,S,S]")
+    if q is not None:
+        q = _chk(q, "q")
+        if tuple(q.shape) != (N, 1, r, r):
+            raise RuntimeError("view_terms: q must be [N,1,r,r]")
+    L = _lib.lib()
+    ws = _sg_workspace(weights.device, L.p3d_view_terms_workspace_bytes(N, r))
+    sums = torch.empty((2,), dtype=torch.float32, device=weights.device)
+    gw = torch.empty_like(weights) if want_grad else None
+    gx = torch.empty_like(xyz) if want_grad else None
+    count = N * r * r
+    with _on(weights.device):
+        rc = L.p3d_view_terms_f32(_p(weights), _p(xyz), _p(gt_alpha), _p(gt_xyz), _p(q), N, r, S, DEPTH_MODES[depth_mode], 1.0 / count,
+                                  1.0 / count, _p(sums), _p(gw), _p(gx), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_view_terms_f32")
+    return sums / count, gw, gx
+
+
+class _ViewTermsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weights, xyz, gt_alpha, gt_xyz, depth_mode, q):
+        terms, gw, gx = _view_terms_impl(weights, xyz, gt_alpha, gt_xyz, depth_mode, q, True)
+        ctx.save_for_backward(gw, gx)
+        return terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gw, gx = ctx.saved_tensors
+        return (gw * g[0] if ctx.needs_input_grad[0] else None), (gx * g[1] if ctx.needs_input_grad[1] else None), None, None, None, None
+
+
+def view_terms(weights, xyz, gt_alpha, gt_xyz, depth_mode, q=None):
+    """The render-resolution terms of one supervised view (p3d_view_terms_f32): a [2] tensor (alpha term, depth term), each the mean
+    over the N r^2 texels as the reference's .mean() takes it.  depth_mode 'z' | 'x' | 'norm'; q: an optional [N,1,r,r] texel weight.
+    The ground truth and the masks carry no gradient.  Under autograd the gradients of weights and xyz are written by the forward
+    launch and multiplied by the incoming cotangents in backward."""
+    if _wants_grad(weights, xyz):
+        return _ViewTermsFn.apply(weights, xyz, gt_alpha, gt_xyz, depth_mode, q)
+    return _view_terms_impl(weights, xyz, gt_alpha, gt_xyz, depth_mode, q, False)[0]
