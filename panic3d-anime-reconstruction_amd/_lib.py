@@ -55,6 +55,28 @@ class ConvArgs(C.Structure):
                [(n, C.c_float) for n in ("alpha", "gain", "clamp")] + [("rgb_channels", C.c_int32), ("w_f16_layout", C.c_int32)]
 
 
+class OptimTensor(C.Structure):
+    """p3d_optim_tensor (include/p3d_optim.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("p", "m", "v", "ema")] + [("numel", C.c_int64), ("aligned16", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimStep(C.Structure):
+    """p3d_optim_step (include/p3d_optim.h)"""
+    _fields_ = [("grad", C.c_void_p), ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("ema_w", C.c_float), ("grad_aligned16", C.c_int32)]
+
+
+class OptimChunk(C.Structure):
+    """p3d_optim_chunk (include/p3d_optim.h)"""
+    _fields_ = [("offset", C.c_int64), ("tensor", C.c_int32), ("count", C.c_int32)]
+
+
+class OptimArgs(C.Structure):
+    """p3d_optim_args (include/p3d_optim.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("tensors", "steps", "chunks")] + [("n_chunks", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_tensors", "mode", "sanitize")] + \
+               [(n, C.c_float) for n in ("grad_scale", "nan_v", "posinf_v", "neginf_v", "eps")] + [("beta1", C.c_double), ("beta2", C.c_double)]
+
+
 P3D_CONV_MMA_F32, P3D_CONV_MMA_F16, P3D_CONV_MMA_F16X2 = 0, 1, 2
 P3D_WLAYOUT_OIK, P3D_WLAYOUT_PLAIN, P3D_WLAYOUT_UP = 0, 1, 2
 
@@ -150,6 +172,15 @@ LOSS_SIGNATURES = {
     "p3d_view_terms_workspace_bytes": (_Z, [_I, _I]),
     "p3d_view_terms_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _Z, _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_optim.h declares (the optimiser step: multi-tensor Adam and the G_ema update)
+OPTIM_SIGNATURES = {
+    "p3d_optim_plan": (_L, [_P, _I, _P, _L]),
+    "p3d_optim_aligned16": (_I, [_P, _I]),
+    "p3d_optim_step_f32": (_I, [C.POINTER(OptimArgs), _P]),
+    "p3d_optim_struct_layout": (_I, [_I, C.POINTER(C.c_size_t), _I]),
+}
+P3D_OPTIM_CHUNK = 4096                                              # include/p3d_optim.h
+P3D_OPTIM_ADAM, P3D_OPTIM_ADAM_EMA, P3D_OPTIM_EMA = 1, 2, 3         # include/p3d_optim.h
 P3D_BLUR_MAX_TAPS = 127                                # include/p3d_loss.h
 P3D_DEPTH_Z, P3D_DEPTH_X, P3D_DEPTH_NORM = 0, 1, 2     # include/p3d_loss.h
 P3D_GRAD_STATS_BYTES = 256 # include/p3d_render_grad.h: u64 at byte 0 of the workspace = samples that ran the MLP backward
@@ -172,7 +203,7 @@ def lib():
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
-                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
+                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()
@@ -183,6 +214,7 @@ def lib():
     return _LIB
 
 
+OPTIM_STRUCT_MIRRORS = {0: OptimTensor, 1: OptimStep, 2: OptimChunk, 3: OptimArgs}  # P3D_OPTIM_STRUCT_* (p3d_optim_struct_layout)
 STRUCT_MIRRORS = {0: Opts, 1: Dumps, 2: PasteArgs, 3: ConvArgs}  # P3D_STRUCT_* -> the ctypes restatement above
 
 
@@ -191,15 +223,16 @@ def check_struct_layouts(L):
     each field in declaration order).  The mirrors are written by hand; p3d_abi_version() alone would not notice a field that
     was added to one side only, or a padding difference."""
     buf = (C.c_size_t * 64)()
-    for which, cls in STRUCT_MIRRORS.items():
-        n = L.p3d_struct_layout(which, buf, 64)
+    for query, which, cls in [("p3d_struct_layout", w, c) for w, c in STRUCT_MIRRORS.items()] + \
+            [("p3d_optim_struct_layout", w, c) for w, c in OPTIM_STRUCT_MIRRORS.items()]:
+        n = getattr(L, query)(which, buf, 64)
         if n <= 0:
-            raise RuntimeError(f"p3d_struct_layout({which}) failed: {n}")
+            raise RuntimeError(f"{query}({which}) failed: {n}")
         mine = [C.sizeof(cls)] + [getattr(cls, name).offset for name, _ in cls._fields_]
         theirs = list(buf[:n])
         if mine != theirs:
             raise RuntimeError(f"{cls.__name__}: the ctypes mirror in _lib.py (size, offsets {mine}) does not match the struct "
-                               f"{SO} was compiled with ({theirs}): include/panic3d_hip.h and _lib.py have diverged")
+                               f"{SO} was compiled with ({theirs}): include/ and _lib.py have diverged")
 
 
 def check(rc, what):

@@ -1770,3 +1770,191 @@ def view_terms(weights, xyz, gt_alpha, gt_xyz, depth_mode, q=None):
     if _wants_grad(weights, xyz):
         return _ViewTermsFn.apply(weights, xyz, gt_alpha, gt_xyz, depth_mode, q)
     return _view_terms_impl(weights, xyz, gt_alpha, gt_xyz, depth_mode, q, False)[0]
+
+
+# ======================================================================================================================
+# The optimiser step (include/p3d_optim.h)
+# ======================================================================================================================
+_OPTIM_STEP_DTYPE = np.dtype([("grad", "<u8"), ("step_size", "<f4"), ("bc2_sqrt", "<f4"), ("ema_w", "<f4"), ("grad_aligned16", "<i4")])
+_OPTIM_STAGING = 2  # pinned staging buffers of a table, used in turn
+
+
+def _optim_is_device(t):
+    return t.is_cuda
+
+
+def _optim_chk(t, name):
+    """A tensor the kernel writes in place: it has to be a float32 device tensor and dense as it is (a copy would take the write)."""
+    if not isinstance(t, torch.Tensor) or not _optim_is_device(t):
+        raise RuntimeError(f"{name} must be a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be torch.float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous: the optimiser step writes it in place")
+    return t
+
+
+class _OptimTable:
+    """What an optimiser uploads ONCE: the static tensor table (p, m, v, ema pointers, numels, alignment flags) and the chunk plan,
+    both in device memory, and what it needs per step: the device buffer of the per-step entries and pinned staging for it.  The
+    staging buffers are used in turn, and each is reused only after the event recorded behind its last copy has completed: the copy
+    engine may still be reading it when the host gets here again.  The device copy of the per-step entries is rewritten in stream order:
+    the steps of one table belong on one stream."""
+
+    def __init__(self, key, device, rows, numels):
+        L = _lib.lib()
+        n = len(rows)
+        tab = (_lib.OptimTensor * n)()
+        for i, (ptrs, numel) in enumerate(zip(rows, numels)):
+            arr = (C.c_void_p * 4)(*ptrs)
+            tab[i].p, tab[i].m, tab[i].v, tab[i].ema = ptrs
+            tab[i].numel, tab[i].aligned16 = numel, L.p3d_optim_aligned16(arr, 4)
+        nm = (C.c_int64 * n)(*numels)
+        self.n_chunks = L.p3d_optim_plan(nm, n, None, 0)
+        if self.n_chunks < 0:
+            _lib.check(int(self.n_chunks), "p3d_optim_plan")
+        plan = (_lib.OptimChunk * max(self.n_chunks, 1))()
+        if self.n_chunks > 0 and L.p3d_optim_plan(nm, n, plan, self.n_chunks) != self.n_chunks:
+            raise RuntimeError("p3d_optim_plan: the plan does not have the size it announced")
+        up = lambda c: torch.frombuffer(bytearray(bytes(c)), dtype=torch.uint8).to(device)
+        self.key, self.device, self.n = key, device, n
+        self.tensors, self.chunks = up(tab), up(plan)
+        nbytes = n * _OPTIM_STEP_DTYPE.itemsize
+        self.steps = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.staging = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(_OPTIM_STAGING)]
+        self.views = [s.numpy().view(_OPTIM_STEP_DTYPE) for s in self.staging]
+        self.events = [None] * _OPTIM_STAGING
+        self.turn = 0
+
+    def upload(self, grad_ptrs, step_sizes, bc2_sqrts, ema_weights):
+        """Fill the next staging buffer and copy it to the device on the current stream; the launch that follows on that stream
+        reads the copy."""
+        i = self.turn
+        self.turn = (i + 1) % _OPTIM_STAGING
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        v = self.views[i]
+        v["grad"], v["step_size"], v["bc2_sqrt"], v["ema_w"] = grad_ptrs, step_sizes, bc2_sqrts, ema_weights
+        v["grad_aligned16"] = (v["grad"] & 15) == 0
+        self.steps.copy_(self.staging[i], non_blocking=True)
+        if self.events[i] is None:
+            self.events[i] = torch.cuda.Event()
+        self.events[i].record()
+
+
+assert _OPTIM_STEP_DTYPE.itemsize == C.sizeof(_lib.OptimStep)
+
+
+def _adam_ema_impl(params, grads, exp_avgs, exp_avg_sqs, emas, step_sizes, bc2_sqrts, ema_weights, beta1, beta2, eps, grad_scale, sanitize,
+                   table, key=None):
+    """The launch of p3d_optim_step_f32.  Lists of equal length; grads / exp_avgs / exp_avg_sqs None = mode EMA, emas None = mode ADAM;
+    an entry of grads may be None (the tensor is skipped), and so may the moments of such a tensor.  key: what _optim_key gives for
+    these tensors.  Returns the table to pass next time."""
+    n = len(params)
+    adam, ema = grads is not None, emas is not None
+    device = params[0].device
+    if key is None:
+        key = _optim_key(params, exp_avgs, exp_avg_sqs, emas)
+    if table is None or table.key != key:
+        table = _OptimTable(key, device, key[1], key[2])
+    if table.n_chunks == 0:
+        return table
+    zeros = [0.0] * n
+    with _on(device):
+        table.upload([0 if g is None else g.data_ptr() for g in grads] if adam else [0] * n, step_sizes if adam else zeros,
+                     bc2_sqrts if adam else zeros, ema_weights if ema else zeros)
+        nan_v, posinf_v, neginf_v = sanitize if sanitize is not None else (0.0, 0.0, 0.0)
+        a = _lib.OptimArgs(tensors=table.tensors.data_ptr(), steps=table.steps.data_ptr(), chunks=table.chunks.data_ptr(), n_chunks=table.n_chunks,
+                           n_tensors=n, mode=_lib.P3D_OPTIM_EMA if not adam else _lib.P3D_OPTIM_ADAM_EMA if ema else _lib.P3D_OPTIM_ADAM,
+                           sanitize=int(sanitize is not None), grad_scale=grad_scale, nan_v=nan_v, posinf_v=posinf_v, neginf_v=neginf_v, eps=eps,
+                           beta1=beta1, beta2=beta2)
+        rc = _lib.lib().p3d_optim_step_f32(C.byref(a), _stream())
+    _lib.check(rc, "p3d_optim_step_f32")
+    return table
+
+
+def _optim_key(params, exp_avgs, exp_avg_sqs, emas):
+    """What a table was built from: the device, (p, m, v, ema) pointers per tensor (0: none) and the numels."""
+    none = [None] * len(params)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    rows = tuple(zip(map(ptr, params), map(ptr, exp_avgs or none), map(ptr, exp_avg_sqs or none), map(ptr, emas or none)))
+    return params[0].device, rows, tuple(p.numel() for p in params)
+
+
+def adam_ema_step(params, grads=None, exp_avgs=None, exp_avg_sqs=None, step_sizes=None, bc2_sqrts=None, *, beta1=0.0, beta2=0.999, eps=1e-8,
+                  grad_scale=1.0, sanitize=None, ema_params=None, ema_weights=None, table=None):
+    """One launch of the optimiser step over any number of tensors (p3d_optim_step_f32; the formulas: include/p3d_optim.h).
+
+    params: the float32 device tensors p.  With grads (a list, an entry None = Adam skips that tensor in this step: p, m, v untouched),
+    exp_avgs, exp_avg_sqs and per tensor step_sizes = lr / (1 - beta1^step), bc2_sqrts = sqrt(1 - beta2^step): Adam.  With ema_params
+    and ema_weights (per tensor, in [0, 1]: the weight of the OLD ema value; 0 copies): ema <- lerp(p, ema, w) on the new p, for
+    every tensor.  Without grads: the EMA update alone.  The gradient is scaled by grad_scale FIRST and cleaned with
+    sanitize = (nan, posinf, neginf) after that; a gradient that is not contiguous is copied (rare), one that is a view into a flat
+    vector is read where it lies.
+
+    The kernel writes through raw pointers, which the version counters do not see: this function bumps `_version` of every tensor
+    the launch wrote (torch.autograd.graph.increment_version), so every cache keyed on a parameter's version (memo.py) sees the step.
+    Returns the uploaded table; pass it back as `table` and it is reused while the tensors stay where they are (the tensors a table
+    was built from were checked then; the gradients, new tensors at every step, are checked at every step)."""
+    params = list(params)
+    n = len(params)
+    adam, ema = grads is not None, ema_params is not None
+    if n == 0:
+        return table
+    if not adam and not ema:
+        raise RuntimeError("adam_ema_step: neither grads nor ema_params: nothing to do")
+    lists = [list(x) if x is not None else None for x in (grads, exp_avgs, exp_avg_sqs, ema_params)]
+    for name, x in zip(("grads", "exp_avgs", "exp_avg_sqs", "ema_params"), lists):
+        if x is not None and len(x) != n:
+            raise RuntimeError(f"adam_ema_step: {name} has {len(x)} entries for {n} params")
+    grads, exp_avgs, exp_avg_sqs, ema_params = lists
+    if adam and (exp_avgs is None or exp_avg_sqs is None or step_sizes is None or bc2_sqrts is None):
+        raise RuntimeError("adam_ema_step: grads need exp_avgs, exp_avg_sqs, step_sizes and bc2_sqrts")
+    for i, p in enumerate(params):
+        if not isinstance(p, torch.Tensor):
+            raise RuntimeError(f"params[{i}] must be a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
+    key = _optim_key(params, exp_avgs if adam else None, exp_avg_sqs if adam else None, ema_params)
+    if table is None or table.key != key:  # tensors this table has not seen: the full checks
+        device = params[0].device
+        for name, ts in (("params", params), ("exp_avgs", exp_avgs if adam else None), ("exp_avg_sqs", exp_avg_sqs if adam else None), ("ema_params", ema_params)):
+            for i, t in enumerate(ts or ()):
+                if t is None and name.startswith("exp_avg"):
+                    continue
+                _optim_chk(t, f"{name}[{i}]")
+                if t.numel() != params[i].numel() or t.device != device:
+                    raise RuntimeError(f"adam_ema_step: {name}[{i}] does not match params[{i}] (numel) or is on another device")
+    wrote = []
+    if adam:
+        f32, device = torch.float32, params[0].device
+        for i, g in enumerate(grads):
+            if g is None:
+                continue
+            if not g.is_contiguous():
+                grads[i] = g = g.contiguous()
+            if g.dtype is not f32 or g.numel() != key[2][i] or g.device != device:
+                _optim_chk(g, f"grads[{i}]")
+                raise RuntimeError(f"adam_ema_step: grads[{i}] does not match params[{i}] (numel) or is on another device")
+            if exp_avgs[i] is None or exp_avg_sqs[i] is None:
+                raise RuntimeError(f"adam_ema_step: params[{i}] has a gradient and no moments")
+            if not bc2_sqrts[i] > 0:
+                raise RuntimeError(f"adam_ema_step: bc2_sqrts[{i}] must be positive")
+            wrote += (params[i], exp_avgs[i], exp_avg_sqs[i])
+        if len(step_sizes) != n or len(bc2_sqrts) != n:
+            raise RuntimeError("adam_ema_step: step_sizes and bc2_sqrts need one entry per tensor")
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0 and eps >= 0.0):
+            raise RuntimeError("adam_ema_step: betas in [0, 1) and eps >= 0")
+        if sanitize is not None:
+            sanitize = tuple(float(x) for x in sanitize)
+            if len(sanitize) != 3:
+                raise RuntimeError("adam_ema_step: sanitize = (nan, posinf, neginf)")
+    if ema:
+        ema_weights = [float(w) for w in ema_weights]
+        if len(ema_weights) != n or not all(0.0 <= w <= 1.0 for w in ema_weights):
+            raise RuntimeError("adam_ema_step: ema_weights needs one entry in [0, 1] per tensor")
+        wrote += ema_params
+    table = _adam_ema_impl(params, grads, exp_avgs, exp_avg_sqs, ema_params, step_sizes, bc2_sqrts, ema_weights, float(beta1), float(beta2), float(eps),
+                           float(grad_scale), sanitize, table, key)
+    wrote = [t for t in wrote if t.numel() > 0]
+    if wrote:
+        torch.autograd.graph.increment_version(wrote)
+    return table
