@@ -150,6 +150,7 @@ P3D_DEV float p3d_partner(float x) {
 
 struct P3dDecodeCfg {
     float coord_scale, crop_limit, cull_thresh;
+    float cull_s_lo, cull_s_hi;  // p3d_cull_band(cull_thresh): see p3d_apply_masks
     int plane_mode, flags;
 };
 
@@ -556,15 +557,31 @@ P3D_DEV void p3d_widen_unless_forced(const P3dDecodeCfg& cfg, f32x16& rgb) {
 }
 
 // masks on raw sigma: renderer.py:138-153,187-198
+// Cull / binarize decide  a < cull_thresh  with a = 1 - exp_nonpos(-softplus(sigma - 1)), the contract's f32 value of
+// A = 1 / (1 + e^-(sigma - 1)).  |a - A| <= E for every float sigma (measured: p3d_cull_band.hpp), and the host puts
+// cull_s_lo = 1 + logit(cull_thresh - delta) and cull_s_hi = 1 + logit(cull_thresh + delta), delta = 16 E, into the cfg.  Outside
+// the band [cull_s_lo, cull_s_hi], |a - A| <= E < delta puts a on the same side of cull_thresh as A, and A is monotone: sigma <
+// cull_s_lo means a < cull_thresh, sigma > cull_s_hi means not.  Inside it (and for NaN) a is evaluated: it is not monotone as
+// computed, so no single critical sigma gives the same bits.  The evaluation is 40 vector instructions against three compares, and
+// the band is some hundred floats wide: when NO lane of the wave is in it the wave skips the evaluation (P3D_CULL_BAND = 0: never).
+#ifndef P3D_CULL_BAND
+#define P3D_CULL_BAND 1
+#endif
 P3D_DEV float p3d_apply_masks(const P3dDecodeCfg& cfg, float px, float pz, float sigma) {
     if (cfg.flags & P3D_FLAG_CROP) {
         if (__builtin_fabsf(px) > cfg.crop_limit || __builtin_fabsf(pz) > cfg.crop_limit) sigma = P3D_SIGMA_MASKED;
     }
     if (cfg.flags & (P3D_FLAG_CULL | P3D_FLAG_BINARIZE)) {
-        float a = 1.0f - p3d_exp_nonpos(-p3d_softplus(sigma - 1.0f));
+        // outside the band a stands for A's side: -inf < cull_thresh, +inf is not (a band with a finite edge has a finite cull_thresh).
+        // (A float and not a lane mask carries the decision to the compare below: the four-slot tolerance kernel, at its register
+        // cap, spills 26 VGPRs as before this way and 105 with a mask.)
+        float a = (sigma < cfg.cull_s_lo) ? -__builtin_inff() : __builtin_inff();
+        const bool in_band = !(sigma < cfg.cull_s_lo || sigma > cfg.cull_s_hi);  // true for NaN
+        if (!P3D_CULL_BAND || __builtin_amdgcn_ballot_w64(in_band) != 0) a = 1.0f - p3d_exp_nonpos(-p3d_softplus(sigma - 1.0f));
+        const bool below = a < cfg.cull_thresh;
         if (cfg.flags & P3D_FLAG_BINARIZE)
-            sigma = (a < cfg.cull_thresh) ? P3D_SIGMA_MASKED : P3D_SIGMA_SOLID;
-        else if (a < cfg.cull_thresh)
+            sigma = below ? P3D_SIGMA_MASKED : P3D_SIGMA_SOLID;
+        else if (below)
             sigma = P3D_SIGMA_MASKED;
     }
     return sigma;

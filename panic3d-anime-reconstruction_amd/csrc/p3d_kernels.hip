@@ -24,6 +24,7 @@
 
 #include "p3d_ray_phases.hpp"
 #include "p3d_render_plan.hpp"
+#include "p3d_cull_band.hpp"
 #include "p3d_phase_timing.hpp"
 
 #define P3D_WAVES_PER_WG 4
@@ -1213,6 +1214,7 @@ static P3dDecodeCfg make_cfg(const p3d_opts* o) {
     c.coord_scale = o->coord_scale;
     c.crop_limit = o->crop_limit;
     c.cull_thresh = o->cull_thresh;
+    p3d_cull_band(o->cull_thresh, &c.cull_s_lo, &c.cull_s_hi);
     c.plane_mode = o->plane_mode;
     c.flags = o->flags;
     return c;

@@ -39,9 +39,37 @@ P3D_DEV float p3d_exp(float x) {
     return (x > P3D_EXP_HI) ? __builtin_inff() : y;
 }
 
+// P3D_CLAMP_MED3 = 1 (shipped): the two clamps of softplus / sigmoid, max(x, P3D_EXP_LO) for x <= 0 and max(x, 0), are one v_med3_f32
+// each.  fmaxf is IEEE maxnum, which quiets a signalling NaN: where the compiler cannot prove that an operand is none (an MFMA
+// accumulator element: the decoder's pre-activations) it puts a canonicalising v_max_f32 x, x, x in front of every fmaxf, the
+// identity on everything an MFMA can produce.  The median form needs none, and on every input but a signalling NaN it is
+// the same function (tests/test_hip_decode_trim.py): a NaN operand makes v_med3_f32 the minimum of the other two, which is the
+// bound that maxnum returns; otherwise the median of {x, lo, hi} with x <= hi is max(x, lo).  0: fmaxf, kept for A/B runs.
+#ifndef P3D_CLAMP_MED3
+#define P3D_CLAMP_MED3 1
+#endif
+// max(x, P3D_EXP_LO) for x <= 0.  (x = -0 comes out as +0; p3d_exp_core gives the same bits for both.)
+P3D_DEV float p3d_clamp_exp_lo(float x) {
+#if P3D_CLAMP_MED3
+    return __builtin_amdgcn_fmed3f(x, P3D_EXP_LO, 0.0f);
+#else
+    return __builtin_fmaxf(x, P3D_EXP_LO);
+#endif
+}
+// max(x, 0).  The upper bound +inf reaches the compiler as an unknown value: it folds a median with a constant +inf back into maxnum.
+P3D_DEV float p3d_max0(float x) {
+#if P3D_CLAMP_MED3
+    float hi = __builtin_inff();
+    asm("" : "+s"(hi));
+    return __builtin_amdgcn_fmed3f(x, 0.0f, hi);
+#else
+    return __builtin_fmaxf(x, 0.0f);
+#endif
+}
+
 // x <= 0: softplus / sigmoid / cull paths.  The clamp makes -inf safe (inf - inf in the reduction); below P3D_EXP_LO the
 // ldexp underflows to exactly 0, so the value equals p3d_exp(x) on the whole domain.
-P3D_DEV float p3d_exp_nonpos(float x) { return p3d_exp_core(__builtin_fmaxf(x, P3D_EXP_LO)); }
+P3D_DEV float p3d_exp_nonpos(float x) { return p3d_exp_core(p3d_clamp_exp_lo(x)); }
 
 P3D_DEV float p3d_log1p01(float z) {
     float q = P3D_L1P_C8;
@@ -59,7 +87,7 @@ P3D_DEV float p3d_log1p01(float z) {
 // torch Softplus(beta=1, threshold=20).  No threshold select: for x > 20 the sum already rounds to x (p3d_numerics.h).
 P3D_DEV float p3d_softplus(float x) {
     float z = p3d_exp_nonpos(-__builtin_fabsf(x));
-    return __builtin_fmaxf(x, 0.0f) + p3d_log1p01(z);
+    return p3d_max0(x) + p3d_log1p01(z);
 }
 
 // 1/d for d in [1,2]: linear seed + three Newton steps, all fma (bit-reproducible; an IEEE division costs ~15 VALU slots)
