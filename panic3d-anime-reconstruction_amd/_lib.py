@@ -179,6 +179,17 @@ OPTIM_SIGNATURES = {
     "p3d_optim_step_f32": (_I, [C.POINTER(OptimArgs), _P]),
     "p3d_optim_struct_layout": (_I, [_I, C.POINTER(C.c_size_t), _I]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_lpips.h declares (LPIPS: the AlexNet trunk's layers, the pool and the head)
+LPIPS_SIGNATURES = {
+    "p3d_lpips_conv_relu_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "p3d_lpips_conv_relu_backward_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "p3d_lpips_pool_f32": (_I, [_P, _L, _I, _I, _P, _P]),
+    "p3d_lpips_pool_backward_f32": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "p3d_lpips_head_workspace_bytes": (_Z, [_I, _L]),
+    "p3d_lpips_head_f32": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _P, _Z, _P]),
+    "p3d_lpips_head_backward_f32": (_I, [_P, _P, _P, _P, _I, _I, _L, _P, _I, _P, _P]),
+}
+P3D_LPIPS_MAX_K, P3D_LPIPS_MAX_STRIDE, P3D_LPIPS_BWD_MAX_CI = 11, 4, 4  # include/p3d_lpips.h
 P3D_OPTIM_CHUNK = 4096                                              # include/p3d_optim.h
 P3D_OPTIM_ADAM, P3D_OPTIM_ADAM_EMA, P3D_OPTIM_EMA = 1, 2, 3         # include/p3d_optim.h
 P3D_BLUR_MAX_TAPS = 127                                # include/p3d_loss.h
@@ -203,7 +214,8 @@ def lib():
                 _build.build()  # (not force: under torch.distributed.run the rank that gets the lock builds, the others find it done)
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
-                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+                + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
+                + list(LPIPS_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

@@ -8,7 +8,8 @@ the caller's modules and torch plumbing.  Random draws come from torch's global 
 as the reference's, so a seeded CPU run of both sees the same numbers.
 
 Not covered: the R1 penalty (see StyleGAN2LossOrthoCondA), the augmentation pipeline (any callable is applied as the reference
-applies its own; the pipe itself is not ported) and LPIPS (any callable returning [N]).
+applies its own; the pipe itself is not ported).  LPIPS is any callable returning [N]; panic3d_amd.lpips.LPIPSLoss() is the HIP one
+(DESIGN.md §4.14).
 """
 import numpy as np
 import torch
@@ -72,8 +73,9 @@ class StyleGAN2LossOrthoCondA:
     A defect of the reference that is not reproduced: its Greg style-mixing lines (:591, :635, :679) name the undefined variables z
     and c, a NameError whenever style_mixing_prob > 0; gen_z and gen_c are used here.
 
-    lpips_model: any callable (image, target) -> [N]; a positive LPIPS weight without one raises here.  The image receives the L1
-    gradient from ops.l1_mean and the LPIPS gradient from torch, both through autograd."""
+    lpips_model: any callable (image, target) -> [N] — panic3d_amd.lpips.LPIPSLoss() for the HIP path, or the trainer's own network,
+    which torch differentiates; a positive LPIPS weight without one raises here.  The image receives the L1 gradient from ops.l1_mean
+    and the LPIPS gradient from the model, both through autograd."""
 
     def __init__(self, device, G, D, lpips_model=None, augment_pipe=None, r1_gamma=10, style_mixing_prob=0,
                  pl_weight=0, pl_batch_shrink=2, pl_decay=0.01, pl_no_weight_grad=False, blur_init_sigma=0, blur_fade_kimg=0,

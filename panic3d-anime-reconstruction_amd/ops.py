@@ -1958,3 +1958,264 @@ def adam_ema_step(params, grads=None, exp_avgs=None, exp_avg_sqs=None, step_size
     if wrote:
         torch.autograd.graph.increment_version(wrote)
     return table
+
+
+# ======================================================================================================================
+# LPIPS, the AlexNet perceptual distance (include/p3d_lpips.h).  Seven device operators (the _impl functions, which
+# the CPU tests replace by torch stand-ins), their checked public forms, and ops.lpips_distance: the whole distance as ONE autograd
+# function, first order, differentiable in the first image only.
+# ======================================================================================================================
+LPIPS_MIN_SIZE = 31  # below it the second pool has no output (H -> (H - 7) // 4 -> // 2 -> // 2)
+
+
+def _lpips_out_hw(Hi, Wi, k, stride, pad):
+    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
+    if not (1 <= k <= _lib.P3D_LPIPS_MAX_K and 1 <= stride <= _lib.P3D_LPIPS_MAX_STRIDE and 0 <= pad < k):
+        raise ValueError(f"lpips convolution: k {k} (1..11), stride {stride} (1..4), pad {pad} (0..k-1)")
+    if Hi + 2 * pad < k or Wi + 2 * pad < k:
+        raise ValueError("lpips convolution: the padded input is smaller than the kernel")
+    return Ho, Wo
+
+
+def _lpips_conv_relu_impl(x, wk, bias, k, stride, pad, shift, scale):
+    x, wk = _chk(x, "x"), _chk(wk, "wk")  # (the first operator of ops.lpips_distance: its images and weights are checked here)
+    N, Ci, Hi, Wi = x.shape
+    Co = wk.shape[2]
+    Ho, Wo = _lpips_out_hw(Hi, Wi, k, stride, pad)
+    out = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.lib().p3d_lpips_conv_relu_f32(_p(x), N, Ci, Hi, Wi, _p(wk), k, Co, Ho, Wo, stride, pad, _p(bias), _p(shift), _p(scale), _p(out),
+                                                _stream())
+    _lib.check(rc, "p3d_lpips_conv_relu_f32")
+    return out
+
+
+def _lpips_conv_relu_backward_impl(g_in, g_head, a, wkb, k, Ci, Hi, Wi, stride, pad, scale):
+    some = g_in if g_in is not None else g_head
+    N, Co, Ho, Wo = some.shape
+    gx = torch.empty((N, Ci, Hi, Wi), dtype=torch.float32, device=some.device)
+    with _on(some.device):
+        rc = _lib.lib().p3d_lpips_conv_relu_backward_f32(_p(g_in), _p(g_head), _p(a), N, Co, Ho, Wo, _p(wkb), k, Ci, Hi, Wi, stride, pad, _p(scale),
+                                                         _p(gx), _stream())
+    _lib.check(rc, "p3d_lpips_conv_relu_backward_f32")
+    return gx
+
+
+def _lpips_pool_impl(x):
+    N, Cc, H, W = x.shape
+    y = torch.empty((N, Cc, (H - 3) // 2 + 1, (W - 3) // 2 + 1), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.lib().p3d_lpips_pool_f32(_p(x), N * Cc, H, W, _p(y), _stream())
+    _lib.check(rc, "p3d_lpips_pool_f32")
+    return y
+
+
+def _lpips_pool_backward_impl(x, g):
+    N, Cc, H, W = x.shape
+    gx = torch.empty_like(x)
+    with _on(x.device):
+        rc = _lib.lib().p3d_lpips_pool_backward_f32(_p(x), _p(g), N * Cc, H, W, _p(gx), _stream())
+    _lib.check(rc, "p3d_lpips_pool_backward_f32")
+    return gx
+
+
+def _lpips_head_impl(a0, a1, lin, v, out, accumulate):
+    """Writes v [N] (this layer's value) and, when out [N] is given, out = v (accumulate False) or out + v."""
+    N, Cc = a0.shape[0], a0.shape[1]
+    HW = a0.numel() // (N * Cc)
+    L = _lib.lib()
+    nbytes = L.p3d_lpips_head_workspace_bytes(N, HW)
+    ws = _sg_workspace(a0.device, nbytes)
+    with _on(a0.device):
+        rc = L.p3d_lpips_head_f32(_p(a0), _p(a1), _p(lin), N, Cc, HW, _p(v), _p(out), int(bool(accumulate)), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_lpips_head_f32")
+
+
+def _lpips_head_backward_impl(a0, a1, lin, g, g_add=None, relu_mask=False):
+    N, Cc = a0.shape[0], a0.shape[1]
+    g_a0 = torch.empty_like(a0)
+    with _on(a0.device):
+        rc = _lib.lib().p3d_lpips_head_backward_f32(_p(a0), _p(a1), _p(lin), _p(g), N, Cc, a0.numel() // (N * Cc), _p(g_add), int(bool(relu_mask)),
+                                                    _p(g_a0), _stream())
+    _lib.check(rc, "p3d_lpips_head_backward_f32")
+    return g_a0
+
+
+def _lpips_chk(t, name, shape=None, ndim=None):
+    t = _chk(t, name)
+    if (ndim is not None and t.ndim != ndim) or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape) if shape is not None else f'{ndim} dimensions'}")
+    return t
+
+
+def lpips_conv_relu(x, wk, bias, k, stride, pad, shift=None, scale=None):
+    """max(corr(in, wk) + bias, 0) in one launch (p3d_lpips_conv_relu_f32): x [N,Ci,H,W]; wk [k*k,Ci,Co] = weight.permute(2, 3, 1, 0);
+    bias [Co]; shift, scale [Ci] (both or neither): in = (x - shift) / scale, zero padding applied after it."""
+    x = _lpips_chk(x, "x", ndim=4)
+    Ci = x.shape[1]
+    wk = _lpips_chk(wk, "wk", ndim=3)
+    if wk.shape[0] != k * k or wk.shape[1] != Ci:
+        raise ValueError(f"wk: shape {tuple(wk.shape)}, expected ({k * k}, {Ci}, Co)")
+    bias = _lpips_chk(bias, "bias", (wk.shape[2],))
+    if (shift is None) != (scale is None):
+        raise ValueError("lpips_conv_relu: shift and scale come together")
+    if shift is not None:
+        shift, scale = _lpips_chk(shift, "shift", (Ci,)), _lpips_chk(scale, "scale", (Ci,))
+    _lpips_out_hw(x.shape[2], x.shape[3], int(k), int(stride), int(pad))
+    return _lpips_conv_relu_impl(x, wk, bias, int(k), int(stride), int(pad), shift, scale)
+
+
+def lpips_conv_relu_backward(g_in, g_head, a, wkb, k, Ci, Hi, Wi, stride, pad, scale=None):
+    """The layer's data gradient (p3d_lpips_conv_relu_backward_f32): the cotangents g_in and g_head (either may be None), masked by the
+    stored output a > 0 (a None: taken as they are, masked already) -> [N,Ci,Hi,Wi].  wkb: stride 1: the flipped, transposed weights [k*k,Co,Ci] (lpips_backward_weights);
+    stride > 1 (the stem): the forward's wk [k*k,Ci,Co], Ci <= 4.  scale [Ci]: the scaling layer's division (the stem only)."""
+    if g_in is None and g_head is None:
+        raise ValueError("lpips_conv_relu_backward: no cotangent")
+    shape = (g_in if g_in is not None else g_head).shape
+    a = _lpips_chk(a, "a", shape, ndim=4) if a is not None else None
+    g_in = _lpips_chk(g_in, "g_in", shape, ndim=4) if g_in is not None else None
+    g_head = _lpips_chk(g_head, "g_head", shape, ndim=4) if g_head is not None else None
+    k, Ci, Hi, Wi, stride, pad = int(k), int(Ci), int(Hi), int(Wi), int(stride), int(pad)
+    if _lpips_out_hw(Hi, Wi, k, stride, pad) != tuple(shape[2:]):
+        raise ValueError("lpips_conv_relu_backward: the cotangent does not have the layer's output size for an input of Hi x Wi")
+    Co = shape[1]
+    wkb = _lpips_chk(wkb, "wkb", (k * k, Co, Ci) if stride == 1 else (k * k, Ci, Co))
+    if stride > 1 and Ci > _lib.P3D_LPIPS_BWD_MAX_CI:
+        raise ValueError(f"lpips_conv_relu_backward: a strided layer's backward takes at most {_lib.P3D_LPIPS_BWD_MAX_CI} input channels")
+    if scale is not None:
+        if stride == 1:
+            raise ValueError("lpips_conv_relu_backward: the scaling layer sits in front of the strided stem only")
+        scale = _lpips_chk(scale, "scale", (Ci,))
+    return _lpips_conv_relu_backward_impl(g_in, g_head, a, wkb, k, Ci, Hi, Wi, stride, pad, scale)
+
+
+def lpips_backward_weights(wk):
+    """wk [k*k,Ci,Co] -> [k*k,Co,Ci] with the taps reversed: the operand of a stride-1 layer's data gradient."""
+    return wk.detach().flip(0).transpose(1, 2).contiguous()
+
+
+def lpips_pool(x):
+    """3 x 3 stride-2 maximum, no padding, floor mode: [N,C,H,W] -> [N,C,(H-3)//2+1,(W-3)//2+1]."""
+    x = _lpips_chk(x, "x", ndim=4)
+    if x.shape[2] < 3 or x.shape[3] < 3:
+        raise ValueError("lpips_pool: the input is smaller than the window")
+    return _lpips_pool_impl(x)
+
+
+def lpips_pool_backward(x, g):
+    """The pool's backward as a gather: each cotangent goes to the first maximum of its window in row-major scan order."""
+    x = _lpips_chk(x, "x", ndim=4)
+    if x.shape[2] < 3 or x.shape[3] < 3:
+        raise ValueError("lpips_pool_backward: the input is smaller than the window")
+    g = _lpips_chk(g, "g", (x.shape[0], x.shape[1], (x.shape[2] - 3) // 2 + 1, (x.shape[3] - 3) // 2 + 1))
+    return _lpips_pool_backward_impl(x, g)
+
+
+def _lpips_head_args(a0, a1, lin):
+    a0 = _lpips_chk(a0, "a0")
+    if a0.ndim < 2:
+        raise ValueError("a0: [N,C,...]")
+    return a0, _lpips_chk(a1, "a1", a0.shape), _lpips_chk(lin.reshape(-1), "lin", (a0.shape[1],))
+
+
+def lpips_head(a0, a1, lin):
+    """One layer's value v [N] = mean over pixels of sum_c lin[c] (a0 / (|a0| + 1e-10) - a1 / (|a1| + 1e-10))^2 (p3d_lpips_head_f32)."""
+    a0, a1, lin = _lpips_head_args(a0, a1, lin)
+    v = torch.empty((a0.shape[0],), dtype=torch.float32, device=a0.device)
+    _lpips_head_impl(a0, a1, lin, v, None, False)
+    return v
+
+
+def lpips_head_backward(a0, a1, lin, g, g_add=None, relu_mask=False):
+    """The head's cotangent of a0 for the cotangent g [N] of its value (p3d_lpips_head_backward_f32); finite where a pixel of a0 is 0.
+    g_add (a0's shape): added to it in the same pass; relu_mask: the sum kept only where a0 > 0 — together the finished cotangent of
+    the layer's pre-activation, which lpips_conv_relu_backward then takes with a=None."""
+    a0, a1, lin = _lpips_head_args(a0, a1, lin)
+    g_add = _lpips_chk(g_add, "g_add", a0.shape) if g_add is not None else None
+    return _lpips_head_backward_impl(a0, a1, lin, _lpips_chk(g.reshape(-1), "g", (a0.shape[0],)), g_add, relu_mask)
+
+
+LPIPS_DOUBLE_BACKWARD_MESSAGE = ("the LPIPS distance's HIP backward is first order only: a gradient of its gradient (create_graph=True) "
+                                 "is not implemented")
+
+
+class _LpipsFn(torch.autograd.Function):
+    """The whole distance (include/p3d_lpips.h): forward 5 convolutions, 2 pools and 5 heads over the pair as one batch of 2N; backward,
+    from the last layer to the first: the pool's gather where a pool follows, the head's backward — which adds the incoming cotangent
+    and applies the mask a_l > 0 in the same pass —, the layer's data gradient of that one tensor.  Only in0 receives a gradient; the weights are constants."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, net):
+        out, saved = _lpips_forward(in0, in1, net)
+        ctx.net, ctx.hw = net, tuple(in0.shape[2:])
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError(LPIPS_DOUBLE_BACKWARD_MESSAGE)
+        return _lpips_backward_once(ctx, g)
+
+
+@torch.autograd.function.once_differentiable
+def _lpips_backward_once(ctx, g):
+    net, acts = ctx.net, ctx.saved_tensors
+    N = acts[0].shape[0] // 2
+    g = g.reshape(-1).contiguous()
+    g_in = None  # the cotangent of a_l that arrives from the layers after it
+    for l in range(len(acts) - 1, -1, -1):
+        wk, bias, wkb, lin, k, stride, pad, pool_after = net["layers"][l]
+        a = acts[l]
+        if pool_after and g_in is not None:
+            g_in = _lpips_pool_backward_impl(a[:N], g_in)
+        gz = _lpips_head_backward_impl(a[:N], a[N:], lin, g, g_in, True)  # a_l > 0 ? g_in + g_head : 0
+        if l > 0:
+            prev = acts[l - 1]
+            Hi, Wi = ((prev.shape[2] - 3) // 2 + 1, (prev.shape[3] - 3) // 2 + 1) if net["layers"][l - 1][7] else tuple(prev.shape[2:])
+            Ci = prev.shape[1]
+        else:
+            (Hi, Wi), Ci = ctx.hw, net["shift"].shape[0]
+        g_in = _lpips_conv_relu_backward_impl(gz, None, None, wkb, k, Ci, Hi, Wi, stride, pad, net["scale"] if l == 0 else None)
+    return g_in, None, None
+
+
+def _lpips_forward(in0, in1, net):
+    N = in0.shape[0]
+    x = torch.cat([in0, in1])  # one launch per layer for the pair: both images share the weights
+    acts = []
+    for l, (wk, bias, wkb, lin, k, stride, pad, pool_after) in enumerate(net["layers"]):
+        x = _lpips_conv_relu_impl(x, wk, bias, k, stride, pad, net["shift"] if l == 0 else None, net["scale"] if l == 0 else None)
+        acts.append(x)
+        if pool_after:
+            x = _lpips_pool_impl(x)
+    v = torch.empty((len(acts), N), dtype=torch.float32, device=in0.device)
+    out = torch.empty((N,), dtype=torch.float32, device=in0.device)
+    for l, a in enumerate(acts):
+        _lpips_head_impl(a[:N], a[N:], net["layers"][l][3], v[l], out, l > 0)
+    return out.view(N, 1, 1, 1), acts
+
+
+def lpips_distance(in0, in1, net):
+    """The LPIPS distance [N,1,1,1] of in0 and in1 [N,3,H,W] (H, W >= 31) on the operands `net` (LPIPS.operands()): shift, scale [3]
+    and per layer (wk, bias, wkb, lin, k, stride, pad, pool_after).  The same launches, hence the same bits, with and without a
+    recorded backward; the backward is first order and reaches in0 only (a target that requires grad raises)."""
+    for name, t in (("in0", in0), ("in1", in1)):
+        if not isinstance(t, torch.Tensor) or t.ndim != 4 or t.shape[1] != net["shift"].shape[0]:
+            raise ValueError(f"{name}: expected [N,{net['shift'].shape[0]},H,W]")
+    if in0.shape != in1.shape:
+        raise ValueError(f"in0 {tuple(in0.shape)} and in1 {tuple(in1.shape)} differ in shape")
+    if min(in0.shape[2:]) < LPIPS_MIN_SIZE:
+        raise ValueError(f"LPIPS needs H, W >= {LPIPS_MIN_SIZE} (the second pool has no output below): got {tuple(in0.shape[2:])}")
+    if torch.is_grad_enabled() and in1.requires_grad:
+        raise NotImplementedError("LPIPS: the gradient with respect to the target (in1) is not implemented: detach it")
+    in0c, in1c = _lpips_image(in0, "in0"), _lpips_image(in1, "in1")
+    if _wants_grad(in0):
+        return _LpipsFn.apply(in0c, in1c.detach(), net)
+    return _lpips_forward(in0c, in1c, net)[0]
+
+
+def _lpips_image(t, name):
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be torch.float32, got {t.dtype}")
+    return t.contiguous()
