@@ -77,6 +77,12 @@ class OptimArgs(C.Structure):
                [(n, C.c_float) for n in ("grad_scale", "nan_v", "posinf_v", "neginf_v", "eps")] + [("beta1", C.c_double), ("beta2", C.c_double)]
 
 
+class EncLayer(C.Structure):
+    """p3d_enc_layer (include/p3d_encoder.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "N", "Ci", "H", "W", "Co", "Ho", "Wo", "k", "stride", "in_", "out", "res", "flags", "plan",
+                                         "reserved")] + [("w_off", C.c_int64), ("b_off", C.c_int64)]
+
+
 P3D_CONV_MMA_F32, P3D_CONV_MMA_F16, P3D_CONV_MMA_F16X2 = 0, 1, 2
 P3D_WLAYOUT_OIK, P3D_WLAYOUT_PLAIN, P3D_WLAYOUT_UP = 0, 1, 2
 
@@ -189,6 +195,19 @@ LPIPS_SIGNATURES = {
     "p3d_lpips_head_f32": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _P, _Z, _P]),
     "p3d_lpips_head_backward_f32": (_I, [_P, _P, _P, _P, _I, _I, _L, _P, _I, _P, _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_encoder.h declares (the conditioning encoder: ResNet layers, front end, the table walk)
+ENCODER_SIGNATURES = {
+    "p3d_enc_conv_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
+    "p3d_enc_conv_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "p3d_enc_conv_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _Z, _P]),
+    "p3d_enc_maxpool_f32": (_I, [_P, _L, _I, _I, _P, _P]),
+    "p3d_enc_prepare_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "p3d_enc_struct_layout": (_I, [C.POINTER(C.c_size_t), _I]),
+    "p3d_encoder_forward_f32": (_I, [C.POINTER(EncLayer), _I, _P, _L, _P, _L, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _P, _Z, _P]),
+    "p3d_encoder_workspace_bytes": (_Z, [C.POINTER(EncLayer), _I]),
+}
+P3D_ENC_KC, P3D_ENC_CUS, P3D_ENC_TILE_64, P3D_ENC_TILE_32, P3D_ENC_MAX_SPLIT, P3D_ENC_RELU = 64, 256, 1, 2, 255, 1  # include/p3d_encoder.h
+P3D_ENC_KIND_CONV, P3D_ENC_KIND_MAXPOOL, P3D_ENC_KIND_PREPARE = 0, 1, 2                                           # include/p3d_encoder.h
 P3D_LPIPS_MAX_K, P3D_LPIPS_MAX_STRIDE, P3D_LPIPS_BWD_MAX_CI = 11, 4, 4  # include/p3d_lpips.h
 P3D_OPTIM_CHUNK = 4096                                              # include/p3d_optim.h
 P3D_OPTIM_ADAM, P3D_OPTIM_ADAM_EMA, P3D_OPTIM_EMA = 1, 2, 3         # include/p3d_optim.h
@@ -215,7 +234,7 @@ def lib():
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
                 + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
-                + list(LPIPS_SIGNATURES.items()):
+                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()
@@ -235,6 +254,10 @@ def check_struct_layouts(L):
     each field in declaration order).  The mirrors are written by hand; p3d_abi_version() alone would not notice a field that
     was added to one side only, or a padding difference."""
     buf = (C.c_size_t * 64)()
+    n = L.p3d_enc_struct_layout(buf, 64)
+    if n <= 0 or list(buf[:n]) != [C.sizeof(EncLayer)] + [getattr(EncLayer, name).offset for name, _ in EncLayer._fields_]:
+        raise RuntimeError(f"EncLayer: the ctypes mirror in _lib.py does not match the struct {SO} was compiled with ({list(buf[:max(n, 0)])}): "
+                           "include/p3d_encoder.h and _lib.py have diverged")
     for query, which, cls in [("p3d_struct_layout", w, c) for w, c in STRUCT_MIRRORS.items()] + \
             [("p3d_optim_struct_layout", w, c) for w, c in OPTIM_STRUCT_MIRRORS.items()]:
         n = getattr(L, query)(which, buf, 64)

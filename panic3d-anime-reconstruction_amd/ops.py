@@ -2219,3 +2219,170 @@ def _lpips_image(t, name):
     if t.dtype != torch.float32:
         raise RuntimeError(f"{name} must be torch.float32, got {t.dtype}")
     return t.contiguous()
+
+
+# ======================================================================================================================
+# The conditioning encoder (include/p3d_encoder.h): a ResNet's layers with folded batch norm, the image front end and
+# the walk of a whole network's table in one C call.  Inference only.  Four device operators (the _impl functions, which the CPU tests
+# replace by torch stand-ins) and their checked public forms.
+# ======================================================================================================================
+def _enc_out_hw(H, W, k, stride):
+    if k not in (1, 3, 7) or stride not in (1, 2):
+        raise ValueError(f"encoder convolution: k {k} (1, 3 or 7), stride {stride} (1 or 2)")
+    pad = (k - 1) // 2
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def enc_resize_hw(H, W, size):
+    """torchvision's Resize(int): the shorter side becomes `size`, the longer one int(size * long / short)."""
+    H, W, size = int(H), int(W), int(size)
+    if size < 1 or H < 1 or W < 1:
+        raise ValueError("encoder: sizes are positive")
+    return (int(size * H / W), size) if W <= H else (size, int(size * W / H))
+
+
+def enc_conv_plan(N, Ci, Co, Ho, Wo, k, stride, force_plan=0):
+    """The host-side plan of one convolution (p3d_enc_conv_plan, no GPU needed): dict(code, tile, split, cps, workgroups, workspace_bytes)."""
+    L = _lib.lib()
+    out = (C.c_int * 4)()
+    code = L.p3d_enc_conv_plan(N, Ci, Co, Ho, Wo, k, stride, int(force_plan), out)
+    if code < 0:
+        _lib.check(code, "p3d_enc_conv_plan")
+    return dict(code=code, tile=out[0], split=out[1], cps=out[2], workgroups=out[3],
+                workspace_bytes=L.p3d_enc_conv_workspace_bytes(N, Ci, Co, Ho, Wo, k, stride, int(force_plan)))
+
+
+def _enc_conv_impl(x, wk, bias, k, stride, res, relu, force_plan):
+    x, wk, bias = _chk(x, "x"), _chk(wk, "wk"), _chk(bias, "bias")
+    res = _chk(res, "res") if res is not None else None
+    N, Ci, H, W = x.shape
+    Co = wk.shape[2]
+    Ho, Wo = _enc_out_hw(H, W, k, stride)
+    L = _lib.lib()
+    out = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=x.device)
+    ws = _sg_workspace(x.device, L.p3d_enc_conv_workspace_bytes(N, Ci, Co, Ho, Wo, k, stride, force_plan))
+    with _on(x.device):
+        rc = L.p3d_enc_conv_f32(_p(x), N, Ci, H, W, _p(wk), k, stride, Co, _p(bias), _p(res), _lib.P3D_ENC_RELU if relu else 0, _p(out), force_plan,
+                                _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_enc_conv_f32")
+    return out
+
+
+def _enc_maxpool_impl(x):
+    x = _chk(x, "x")
+    N, Cc, H, W = x.shape
+    y = torch.empty((N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.lib().p3d_enc_maxpool_f32(_p(x), N * Cc, H, W, _p(y), _stream())
+    _lib.check(rc, "p3d_enc_maxpool_f32")
+    return y
+
+
+def _enc_prepare_impl(img, mean, std, h, w):
+    img, mean, std = _chk(img, "img"), _chk(mean, "mean"), _chk(std, "std")
+    N, Cc, H, W = img.shape
+    out = torch.empty((2 * N, 3, h, w), dtype=torch.float32, device=img.device)
+    with _on(img.device):
+        rc = _lib.lib().p3d_enc_prepare_f32(_p(img), N, Cc, H, W, _p(mean), _p(std), h, w, _p(out), _stream())
+    _lib.check(rc, "p3d_enc_prepare_f32")
+    return out
+
+
+def enc_conv(x, wk, bias, k, stride=1, res=None, relu=False, force_plan=0):
+    """[relu](corr(x, wk) + bias [+ res]) (p3d_enc_conv_f32): x [N,Ci,H,W]; wk [k*k,Ci,Co] = weight.permute(2, 3, 1, 0); bias [Co]; res
+    None or [N,Co,Ho,Wo]; k 1, 3 or 7, stride 1 or 2, pad (k - 1) / 2.  force_plan: 0 chooses, else (tile << 8) | split (enc_conv_plan)."""
+    x = _lpips_chk(x, "x", ndim=4)
+    k, stride = int(k), int(stride)
+    Ho, Wo = _enc_out_hw(x.shape[2], x.shape[3], k, stride)
+    wk = _lpips_chk(wk, "wk", (k * k, x.shape[1], wk.shape[2] if isinstance(wk, torch.Tensor) and wk.ndim == 3 else -1))
+    bias = _lpips_chk(bias, "bias", (wk.shape[2],))
+    if res is not None:
+        res = _lpips_chk(res, "res", (x.shape[0], wk.shape[2], Ho, Wo))
+    return _enc_conv_impl(x, wk, bias, k, stride, res, bool(relu), int(force_plan))
+
+
+def enc_maxpool(x):
+    """3 x 3 stride-2 maximum with padding 1 (the padding never wins): [N,C,H,W] -> [N,C,(H-1)//2+1,(W-1)//2+1]."""
+    return _enc_maxpool_impl(_lpips_chk(x, "x", ndim=4))
+
+
+def enc_prepare(img, mean, std, size):
+    """The encoder's front end in one launch (p3d_enc_prepare_f32): img [N,C>=3,H,W] in [0, 1] -> [2N,3,h,w]: the first three channels
+    resized bilinearly (align_corners=False, no antialiasing) to enc_resize_hw(H, W, size) and normalised by mean / std [3]; rows N..2N-1
+    hold the same of the horizontally mirrored image."""
+    img = _lpips_chk(img, "img", ndim=4)
+    if img.shape[1] < 3:
+        raise ValueError(f"img: shape {tuple(img.shape)}, expected at least three channels")
+    mean, std = _lpips_chk(mean, "mean", (3,)), _lpips_chk(std, "std", (3,))
+    h, w = enc_resize_hw(img.shape[2], img.shape[3], size)
+    return _enc_prepare_impl(img, mean, std, h, w)
+
+
+class EncoderProgram:
+    """A whole network as p3d_encoder_forward_f32 takes it: the table of layer records, one weight blob, the activation arena.
+    records: dicts with kind ('conv' | 'maxpool' | 'prepare'), shape (N, Ci, H, W), out_shape (N', Co, Ho, Wo), src / dst / res (buffer
+    indices, res None), k, stride, relu, plan, and w / b (conv: wk, bias; prepare: mean, std).  buf_len: floats per buffer."""
+    KINDS = {"conv": _lib.P3D_ENC_KIND_CONV, "maxpool": _lib.P3D_ENC_KIND_MAXPOOL, "prepare": _lib.P3D_ENC_KIND_PREPARE}
+
+    def __init__(self, records, buf_len, device):
+        self.records, self.device = list(records), torch.device(device)
+        self.table = (_lib.EncLayer * len(self.records))()
+        parts, off = [], 0
+        for i, r in enumerate(self.records):
+            t = self.table[i]
+            t.kind = self.KINDS[r["kind"]]
+            t.N, t.Ci, t.H, t.W = r["shape"]
+            _, t.Co, t.Ho, t.Wo = r["out_shape"]
+            t.k, t.stride = (r["k"], r["stride"]) if r["kind"] == "conv" else (0, 0)
+            t.in_, t.out, t.res = r["src"], r["dst"], -1 if r.get("res") is None else r["res"]
+            t.flags, t.plan, t.reserved = (_lib.P3D_ENC_RELU if r.get("relu") else 0), int(r.get("plan", 0)), 0
+            offs = []
+            for name in ("w", "b"):
+                if r["kind"] == "maxpool":
+                    offs.append(0)
+                    continue
+                v = r[name].detach().to(torch.float32).reshape(-1)
+                offs.append(off)
+                parts.append(v)
+                off += v.numel()
+            t.w_off, t.b_off = offs
+        self.weights = torch.cat(parts).to(self.device).contiguous() if parts else torch.zeros(1, device=self.device)
+        self.n_bufs = len(buf_len)
+        self.buf_len = (C.c_int64 * self.n_bufs)(*[int(n) for n in buf_len])
+        offs, at = [], 0
+        for n in buf_len:
+            offs.append(at)
+            at += (int(n) + 63) // 64 * 64  # every buffer starts on a 256-byte boundary
+        self.buf_off = (C.c_int64 * self.n_bufs)(*offs)
+        self.arena = torch.empty((max(at, 1),), dtype=torch.float32, device=self.device)
+        self.launches = None  # (set by the first run: kernels per call)
+
+    def buffer(self, b, shape):
+        n = 1
+        for s in shape:
+            n *= int(s)
+        return self.arena[self.buf_off[b]:self.buf_off[b] + n].view(*shape)
+
+
+def _encoder_forward_impl(prog):
+    _chk(prog.arena, "the program's arena"), _chk(prog.weights, "the program's weights")
+    L = _lib.lib()
+    ws = _sg_workspace(prog.device, L.p3d_encoder_workspace_bytes(prog.table, len(prog.records)))
+    with _on(prog.device):
+        rc = L.p3d_encoder_forward_f32(prog.table, len(prog.records), _p(prog.weights), prog.weights.numel(), _p(prog.arena), prog.arena.numel(),
+                                       prog.buf_off, prog.buf_len, prog.n_bufs, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_encoder_forward_f32")
+
+
+def encoder_forward(prog, img, src=0):
+    """Run a whole EncoderProgram in ONE call into the library: img is copied into buffer `src` of the arena, every layer is launched
+    on the current stream; the results are read with prog.buffer(index, shape) (views of the arena: clone what has to outlive the next call)."""
+    if not isinstance(prog, EncoderProgram):
+        raise TypeError("encoder_forward: an EncoderProgram")
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.float32 or img.device != prog.arena.device:
+        raise RuntimeError(f"img must be a torch.float32 tensor on {prog.arena.device}")
+    if img.numel() != prog.buf_len[src]:
+        raise ValueError(f"img: {img.numel()} values, the program was built for {prog.buf_len[src]}")
+    prog.arena[prog.buf_off[src]:prog.buf_off[src] + img.numel()].copy_(img.reshape(-1))
+    _encoder_forward_impl(prog)
+    return prog

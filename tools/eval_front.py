@@ -214,9 +214,14 @@ def run(G, data, out, subset="front", mesh=False, limit=None, device="cuda", see
 
 
 # ---- preparation on a box that has the reference tree and its assets (generate.py:27-96; NOT runnable here) ---------------------------
-def prepare(reference, data, limit=None, device="cuda"):
+TAGGER_CKPT = "./_train/danbooru_tagger/runs/waning_kate_vulcan0001/checkpoints/epoch=0022-val_f2=0.4461-val_loss=0.0766.ckpt"  # katebackbone.py:13-14
+
+
+def prepare(reference, data, limit=None, device="cuda", encoder="reference"):
     """Write the prepared layout with the reference's own data backend and pre-processing networks.  Mirrors generate.py:27-47,68-96
-    and measure.py:20-27,108-122; run it from the root of the reference repository's environment."""
+    and measure.py:20-27,108-122; run it from the root of the reference repository's environment.
+    encoder='hip': resnet_chonk.npy comes from panic3d_amd.ResnetFeatureExtractorPCA (the HIP encoder) reading the same pca.pkl and
+    the tagger's checkpoint — best-effort: neither file was available to check the loaders against."""
     os.chdir(reference)
     sys.path[:0] = [reference]
     import _util.util_v1 as uutil
@@ -227,7 +232,12 @@ def prepare(reference, data, limit=None, device="cuda"):
     bns = [f"daredemoE/fandom_align/{bn}/front" for bn in uutil.read_bns("./_data/lustrous/subsets/daredemoE_test.csv")][:limit]
     aligndata = uutil.pload("./_data/lustrous/renders/daredemoE/fandom_align_alignment.pkl")
     rmline_model = rmline_wrapper.RMLineWrapper(("rmlineE_rmlineganA_n04", 199)).eval().to(device)
-    resnet = ResnetFeatureExtractorPCA("./_data/lustrous/preprocessed/minna_resnet_feats_ortho/pca.pkl", 512).eval().to(device)
+    if encoder == "hip":
+        import panic3d_amd
+        resnet = panic3d_amd.ResnetFeatureExtractorPCA("./_data/lustrous/preprocessed/minna_resnet_feats_ortho/pca.pkl", 512, num_classes=None)
+        resnet.load_checkpoint(TAGGER_CKPT).eval().to(device)
+    else:
+        resnet = ResnetFeatureExtractorPCA("./_data/lustrous/preprocessed/minna_resnet_feats_ortho/pca.pkl", 512).eval().to(device)
     names = []
     for bn in bns:
         x = dk[bn]
@@ -258,6 +268,8 @@ def main(argv=None):
     pr.add_argument("--reference", required=True)
     pr.add_argument("--data", required=True)
     pr.add_argument("--limit", type=int)
+    pr.add_argument("--encoder", choices=("reference", "hip"), default="reference",
+                    help="hip: the conditioning features from panic3d_amd's HIP encoder instead of the reference's torchvision module (unchecked loaders)")
     rn = sub.add_parser("run")
     rn.add_argument("--network", required=True)
     rn.add_argument("--reference", required=True, help="root of the reference repository (unpickling needs dnnlib / legacy / torch_utils)")
@@ -269,7 +281,7 @@ def main(argv=None):
     rn.add_argument("--exact", action="store_true", help="exact-contract final pass (default: the renderer's tolerance mode)")
     a = ap.parse_args(argv)
     if a.cmd == "prepare":
-        print(json.dumps({"prepared": len(prepare(os.path.abspath(a.reference), os.path.abspath(a.data), a.limit))}))
+        print(json.dumps({"prepared": len(prepare(os.path.abspath(a.reference), os.path.abspath(a.data), a.limit, encoder=a.encoder))}))
         return
     if not torch.cuda.is_available():
         raise SystemExit("eval_front run needs an MI355X: the HIP path has no CPU fallback")

@@ -2,7 +2,9 @@
 """The per-subject flow of _scripts/eval/generate.py:80-151 on the MI355X path, at the released model's sizes, with
 random-init weights and a synthetic illustration (the checkpoint and the AnimeRecon data are not in this environment):
 density grid 256^3 (get_eg3d_volume), then 4 orthographic + 12 perspective views through G.f with the front-view paste.
-Prints a timing breakdown (one JSON line)."""
+Prints a timing breakdown (one JSON line).  --encoder hip: resnet_chonk comes from panic3d_amd.ResnetFeatureExtractorPCA run on the
+synthetic illustration (seeded weights and a seeded orthonormal PCA: the tagger's checkpoint is not here either) instead of torch.randn, and
+the line gains encoder_ms, the extractor's call for one subject."""
 import os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -33,6 +35,21 @@ with torch.no_grad():
 G.set_force_sigmoid(True)
 G.neural_rendering_resolution = 128
 cond = {"image_ortho_front": torch.rand(1, 3, 512, 512, device=dev), "resnet_chonk": torch.randn(1, 64, 8, 8, device=dev)}
+encoder_ms = None
+if "--encoder" in sys.argv:
+    if sys.argv[sys.argv.index("--encoder") + 1] != "hip":
+        raise SystemExit("--encoder: 'hip' (the default is a random conditioning tensor)")
+    gen = torch.Generator().manual_seed(0)
+    rfe = P.ResnetFeatureExtractorPCA(None, 64)
+    rfe.set_pca(torch.linalg.qr(torch.randn(2048, 64, generator=gen))[0].t(), torch.rand(2048, generator=gen))
+    rfe.to(dev)
+    rfe(cond["image_ortho_front"])  # warm-up
+    torch.cuda.synchronize()
+    te = time.perf_counter()
+    chonk = rfe(cond["image_ortho_front"])  # [2,64,8,8]: the image and its mirror
+    torch.cuda.synchronize()
+    encoder_ms = (time.perf_counter() - te) * 1e3
+    cond["resnet_chonk"] = chonk[None, 0]  # generate.py:92
 opts = {"triplane_crop": 0.1, "cull_clouds": 0.5,
         "paste_params": {"mode": "default", "thresh_weight": 0.95, "thresh_edges": 0.02, "thresh_occ": 0.05, "offset_occ": 0.01,
                          "thresh_dxyz": 0.000005}}
@@ -108,4 +125,4 @@ print(json.dumps({"one_view_f_ms": (t1 - t0) * 1e3, "density_grid_256_ms": (t2 -
                   "views_with_paste_ms": (t3 - tm1) * 1e3, "ms_per_view": (t3 - tm1) * 1e3 / len(views), "ms_per_view_next_subjects": (t3b - t3) * 1e3 / len(views),
                   "subject_total_ms": (t3 - t0 - (tm0 - t2)) * 1e3, "ms_per_view_planes_cached": (t4 - t3) * 1e3 / len(views), "ms_per_view_all_views_one_call": (t6 - t5) * 1e3 / len(views),
                   "ms_per_view_all_views_one_call_sr_f16_operands": (t8 - t7) * 1e3 / len(views), "sr_f16_vs_fp32_psnr_db": sr_f16_psnr, "mean_alpha_last_view": float(o["image_weights"].mean()),
-                  "paste_mask_mean_last_view": float(o["paste"]["mask"].mean())}))
+                  "paste_mask_mean_last_view": float(o["paste"]["mask"].mean()), **({"encoder_ms": encoder_ms} if encoder_ms is not None else {})}))
