@@ -1380,6 +1380,19 @@ int p3d_phase_read(unsigned long long* out, int n, int reset) {
     }
     return P3D_PH_N;
 }
+// ... and the per-wave records of the LAST k_render launch: out[4 * i ..] = {start, end (100 MHz ticks), block, XCD} of wave slot i < n
+int p3d_phase_read_waves(unsigned long long* out, int n) {
+    if (!out || n < 0 || n > P3D_WAVE_RECORDS) return -1;
+    P3dWaveRecord* v = (P3dWaveRecord*)malloc(sizeof(P3dWaveRecord) * (size_t)(n > 0 ? n : 1));
+    if (!v) return -1;
+    const bool ok = hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpyFromSymbol(v, HIP_SYMBOL(g_p3d_wave), sizeof(P3dWaveRecord) * (size_t)n) == hipSuccess;
+    for (int i = 0; ok && i < n; ++i) {
+        out[4 * i] = v[i].t0; out[4 * i + 1] = v[i].t1; out[4 * i + 2] = v[i].block; out[4 * i + 3] = v[i].xcc;
+    }
+    free(v);
+    return ok ? n : -1;
+}
 #endif
 int p3d_render_plan_info(int N, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits, int64_t* out, int cap) {
     if (!opts) return P3D_E_ARG;
@@ -1455,7 +1468,7 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     p.white_back = (opts->flags & P3D_FLAG_WHITE_BACK) ? 1 : 0;
     p.cfg = make_cfg(opts);
     p.tile_w = pl.tile_w; p.tiles_x = pl.tiles_x; p.tiles_per_img = pl.tiles_per_img; p.ntiles = pl.ntiles;
-    p.lds_rows = pl.lds_rows; p.swz = pl.swz; p.blocked = pl.blocked;
+    p.lds_rows = pl.lds_rows; p.order = pl.order;
     hipLaunchKernelGGL(k_minmax_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, p.gminmax, p.per_view_clamp ? N : 0);
     auto launch = [&](void (*kernel)(RenderParams)) {
         hipError_t e = p3d_ensure_dynamic_lds(kernel, pl.lds_bytes);

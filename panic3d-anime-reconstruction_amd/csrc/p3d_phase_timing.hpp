@@ -6,6 +6,11 @@
 // wave ends.  p3d_phase_read() (exported only by this build) copies the totals out.  A stamp waits for its own result only,
 // so a section is charged the ISSUE time of its instructions plus whatever it waited for itself; the stamps cost ~10 % of a
 // wave's cycles, which is why the table gives shares and not milliseconds.
+//
+// Each wave also leaves one record of its own in g_p3d_wave (slot = blockIdx.x * waves per block + wave, the launches of at
+// most P3D_WAVE_RECORDS waves): the device-wide real-time counter (s_memrealtime: 100 MHz, one clock for all XCDs, unlike the
+// per-XCD shader clock) when it started and when it ended, its block index and the XCD it really ran on (HW_REG_XCC_ID).
+// p3d_phase_read_waves() copies them out; tools/phase_timing.py --xcd prints when the last wave of each XCD ended.
 #pragma once
 
 #ifdef P3D_PHASE_TIMING
@@ -26,9 +31,12 @@ enum P3dPhase {
     P3D_PH_N
 };
 __device__ unsigned long long g_p3d_phase[P3D_PH_N];
+#define P3D_WAVE_RECORDS 65536
+struct P3dWaveRecord { unsigned long long t0, t1; unsigned block, xcc; };
+__device__ P3dWaveRecord g_p3d_wave[P3D_WAVE_RECORDS];
 
 struct P3dPhaseClock {
-    unsigned long long first, last, acc[P3D_PH_N];
+    unsigned long long first, last, real0, acc[P3D_PH_N];
     __device__ __forceinline__ static unsigned long long now() {
         unsigned long long t;
         __builtin_amdgcn_sched_barrier(0);
@@ -36,9 +44,17 @@ struct P3dPhaseClock {
         __builtin_amdgcn_sched_barrier(0);
         return t;
     }
+    __device__ __forceinline__ static unsigned long long real_now() {
+        unsigned long long t;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        return t;
+    }
     __device__ __forceinline__ void start() {
 #pragma unroll
         for (int q = 0; q < P3D_PH_N; ++q) acc[q] = 0ull;
+        real0 = real_now();
         first = last = now();
     }
     __device__ __forceinline__ void mark(int slot) {
@@ -52,6 +68,14 @@ struct P3dPhaseClock {
         if ((threadIdx.x & 63) == 0) {
 #pragma unroll
             for (int q = 0; q < P3D_PH_N; ++q) atomicAdd(&g_p3d_phase[q], acc[q]);
+            const unsigned long long slot = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+            if (slot < P3D_WAVE_RECORDS) {
+                unsigned xcc;
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+                P3dWaveRecord r;
+                r.t0 = real0; r.t1 = real_now(); r.block = blockIdx.x; r.xcc = xcc;
+                g_p3d_wave[slot] = r;
+            }
         }
     }
 };

@@ -9,6 +9,7 @@
 #pragma once
 #include "p3d_decode.hpp"
 #include "p3d_importance.hpp"
+#include "p3d_render_plan.hpp"
 
 struct RenderParams {
     const float* planes;  // [N][3][H][W][32]
@@ -33,30 +34,17 @@ struct RenderParams {
     int lds_rows;     // rows (of 32 floats) of per-wave LDS
     int rng;          // p3d_render_rng_f32: the two draws come from the counter-based generator of include/p3d_numerics.h
     uint32_t seed_lo, seed_hi;
-    int swz;          // XCD swizzle run length (blocks)
-    int blocked;      // k_render: tiles ordered by 16 x 16-tile super-tiles, one per XCD run (p3d_render_tile_ray)
+    P3dTileOrder order;  // k_render: the XCD tile order (p3d_render_plan.hpp)
     P3dDecodeCfg cfg;
 };
 
 // The 32-ray tile of wave `wave` of this block in k_render, after the XCD-aware block swizzle: hardware places block b on XCD
 // b % 8; give each XCD a contiguous range of tiles so that the plane texels its rays touch stay in that XCD's L2.
-// Each XCD gets runs of `swz` consecutive blocks, the runs interleaved round-robin over the 8 XCDs: contiguous enough for
-// L2 reuse, fine enough that the XCDs finish together although the early-outs make the work per tile uneven.
+// Each XCD gets runs of consecutive blocks: contiguous enough for L2 reuse, fine enough that the XCDs finish together although
+// the early-outs make the work per tile uneven.  The orders themselves: p3d_tile_of_block / p3d_tile_screen (p3d_render_plan.hpp),
+// which the host evaluates too.
 P3D_DEV long long p3d_render_wave_tile(const RenderParams& p, int wave) {
-    long long nblk = gridDim.x, b = blockIdx.x;
-    const long long swz = p.swz;
-    long long full = (nblk / (8 * swz)) * (8 * swz);
-    long long bs = b;
-    if (b < full) {
-        long long slot = b >> 3, x = b & 7;  // slot-th block of XCD x
-        // p.blocked (round 5): a run is one 16 x 16-tile SUPER-TILE (below); XCD x takes element (x + g) % 8 of group g of eight runs,
-        // so that over its runs it visits every column of super-tiles (the subject sits in the middle columns: a fixed column per
-        // XCD would leave the XCDs of the outer columns idle early)
-        const long long g = slot / swz, xr = p.blocked ? ((x + g) & 7) : x;
-        bs = g * (8 * swz) + xr * swz + (slot % swz);
-    }
-    const int nwaves = blockDim.x >> 6;
-    return bs * nwaves + wave;
+    return p3d_tile_of_block(p.order, gridDim.x, blockIdx.x, blockDim.x >> 6, wave, p.tiles_x, p.tiles_per_img);
 }
 
 struct P3dTileRay { long long n, r; };  // view, ray of the view (may lie past the last ray: the caller clamps)
@@ -64,28 +52,16 @@ struct P3dTileRay { long long n, r; };  // view, ray of the view (may lie past t
 // lane j's ray of k_render's tile
 P3D_DEV P3dTileRay p3d_render_tile_ray(const RenderParams& p, long long tile, int j) {
     P3dTileRay o;
-    o.n = tile / p.tiles_per_img;
-    const long long tl = tile - o.n * p.tiles_per_img;
     if (p.tile_w > 0) {
-        long long ty = tl / p.tiles_x, tx = tl - ty * p.tiles_x;
-        if (p.blocked) {
-            // Blocked tile order (round 5): consecutive tiles fill a SUPER-TILE of 16 x 16 tiles (128 x 64 pixels)
-            // before the next one starts, and the XCD swizzle above hands an XCD whole super-tiles — so the ~256 waves resident on an
-            // XCD march through a compact screen block whose footprint in the three planes (x-extent 1/4, y-extent 1/8 of the image:
-            // ~0.3 + 2.1 + 1.0 MB) fits that XCD's 4 MB L2.  Row-major order gave an XCD four full-width tile rows: the whole xz plane
-            // (8.4 MB) streamed through every L2 (measured round 4: the 25 MB of planes fetched ~5 x per XCD).  A pure permutation of
-            // which wave renders which tile: results are bit-identical.  The host sets it when the tile grid divides into super-tiles.
-            const long long st = tl >> 8;
-            const int q = (int)(tl & 255), SX = p.tiles_x >> 4;
-            tx = (st % SX) * 16 + (q & 15);
-            ty = (st / SX) * 16 + (q >> 4);
-        }
+        const P3dTileXY t = p3d_tile_screen(p.order, tile, p.tiles_x, p.tiles_per_img);
+        o.n = t.n;
         // 8x4 pixel tile in Morton-like lane order: every lane quad is a 2x2 pixel block, so the quad's four gathers of a
         // tap fall into 1-2 cache lines (the L1 coalesces within a quad; rocprof: TCP accesses/instr 48 -> see DESIGN.md)
         const int lx = (j & 1) | ((j >> 1) & 6), ly = ((j >> 1) & 1) | ((j >> 3) & 2);
-        o.r = (ty * 4 + ly) * p.tile_w + tx * 8 + lx;
+        o.r = (t.ty * 4 + ly) * p.tile_w + t.tx * 8 + lx;
     } else {
-        o.r = tl * 32 + j;
+        o.n = tile / p.tiles_per_img;
+        o.r = (tile - o.n * p.tiles_per_img) * 32 + j;
     }
     return o;
 }

@@ -3,6 +3,7 @@
 // order.  Host code only (no HIP headers): tests/test_render_plan.py compiles it into a plain host program.
 //   p3d_render_tcg / p3d_render_occ / p3d_render_slots_occ   per-instantiation rules, shared with the kernels' template defaults
 //                                                            and __launch_bounds__
+//   p3d_tile_of_block / p3d_tile_screen   k_render's tile order itself, compiled for the host AND the device (the kernel calls them)
 //   p3d_render_plan              the plan of one launch: a pure function of its shape and options
 //   p3d_render_plan_workspace_bytes   what p3d_render_workspace_bytes answers
 #pragma once
@@ -22,6 +23,110 @@ constexpr bool p3d_render_tcg(int NF, bool DUMP, bool EARLY) { return NF == 96 &
 constexpr int p3d_render_occ(int NF, bool TCG) { return (NF >= 96 && !TCG) ? 1 : 2; }
 // ... and k_render_slots<SLOTS, NF, FAST>'s: two for the four-slot tolerance-mode ones, one for the others (see that kernel)
 constexpr int p3d_render_slots_occ(int SLOTS, bool FAST) { return (SLOTS == 4 && FAST) ? 2 : 1; }
+
+// ---- k_render's tile order: ONE definition for the kernel (p3d_ray_phases.hpp), the plan below, tests/test_tile_order_cpu.py and
+// tools/xcd_load_model.py (both through tests/tile_order_host.cpp).  Hardware places block b on XCD b % 8 and nothing moves work
+// between XCDs afterwards: the order decides which screen area an XCD's L2 serves and how evenly the uneven tiles (early-outs)
+// add up per XCD.  A pure permutation of which wave renders which tile: results are bit-identical under every order.
+#if defined(__HIPCC__)
+#define P3D_HD __host__ __device__ __forceinline__
+#else
+#define P3D_HD static inline
+#endif
+
+struct P3dTileOrder {
+    int swz;      // blocks of one XCD run
+    int blocked;  // round 5: a run is one 16 x 16-tile super-tile, XCD x takes element (x + g) % 8 of group g of eight runs
+    int pieces;   // round 12: a run is one pw x ph-tile piece; the piece of column c, row r belongs to XCD (xa * c + r + xs * (r / 8)) % 8
+    int pw, ph, xa, xs;
+};
+
+// The pieces and the rule the plan takes: 2 x 8 tiles (16 x 32 pixels, 4 workgroups of 4 waves), piece (c, r) to XCD (c + r) % 8.
+// Of the rules the model (tools/xcd_load_model.py, profiles/r12_xcd_model.txt) finds no worse than the round-5 order on any view of
+// its sweep, the one that measured fastest: with a = 1 an XCD's pieces of neighbouring columns are
+// diagonal neighbours, so what it holds at a time is a diagonal band of the screen, not scattered pieces.
+#ifndef P3D_PIECE_W
+#define P3D_PIECE_W 2
+#define P3D_PIECE_H 8
+#define P3D_XCD_RULE_A 1
+#define P3D_XCD_RULE_S 0
+#endif
+
+// Turns `t` into the piece order of pw x ph-tile pieces under the rule (xa, xs) if a view of tiles_x x tiles_y tiles, rendered by
+// workgroups of nw waves, can take it: whole pieces, a whole number of workgroups per piece, a multiple of 8 piece rows (every
+// column then gives every XCD the same number of pieces, and an XCD visits every column), and of the rows an XCD gets as many in
+// the inner half of the view as in the outer half (the subject sits in the middle).  Otherwise leaves t alone; returns whether.
+static inline bool p3d_piece_order(P3dTileOrder& t, long long tiles_x, long long tiles_y, int nw, int pw, int ph, int xa, int xs) {
+    if (pw <= 0 || ph <= 0 || tiles_x <= 0 || tiles_x % pw || tiles_y % ph || (pw * ph) % nw || (tiles_y / ph) % 8) return false;
+    const long long PC = tiles_x / pw, PR = tiles_y / ph;
+    long long inner[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (long long r = PR / 4; r < PR - PR / 4; ++r)
+        for (long long c = 0; c < PC; ++c) ++inner[(xa * c + r + xs * (r / 8)) & 7];
+    for (int x = 0; x < 8; ++x)
+        if (2 * inner[x] != PC * PR / 8) return false;
+    t.pieces = 1;
+    t.swz = pw * ph / nw;
+    t.pw = pw; t.ph = ph; t.xa = xa; t.xs = xs;
+    return true;
+}
+
+// the tile of wave `wave` of block b of a grid of nblk blocks of nwaves waves (tiles >= ntiles: the padding of the last block)
+P3D_HD long long p3d_tile_of_block(const P3dTileOrder& t, long long nblk, long long b, int nwaves, int wave, int tiles_x,
+                                   long long tiles_per_img) {
+    const long long swz = t.swz;
+    long long bs = b;
+    if (t.pieces) {
+        // XCD x = b % 8 walks ITS pieces view by view and, inside a view, column by column: in a column it owns one row of every
+        // 8 (rows r, r + 8, ...).  The 256 waves an XCD holds at a time cover as many tiles as a super-tile did, in as many tile
+        // columns (x-extent) and as many tile rows per column (y-extent in total).  The plan takes this order only where the
+        // views divide into whole pieces and every XCD owns the same number of them, so there is no remainder.
+        const int x = (int)(b & 7), PC = tiles_x / t.pw, per_img = (int)(tiles_per_img / (t.pw * t.ph)), per_xcd = per_img >> 3;
+        const int per_col = per_xcd / PC;  // = piece rows / 8
+        const long long slot = b >> 3, k = slot / swz;
+        const int n = (int)(k / per_xcd), kk = (int)(k - (long long)n * per_xcd), c = kk / per_col, j = kk - c * per_col;
+        const int r = ((x - t.xa * c - t.xs * j) & 7) + 8 * j;
+        bs = ((long long)n * per_img + (long long)r * PC + c) * swz + (slot - k * swz);
+    } else {
+        const long long full = (nblk / (8 * swz)) * (8 * swz);
+        if (b < full) {
+            const long long slot = b >> 3, x = b & 7;  // slot-th block of XCD x
+            // blocked: over its runs an XCD visits every column of super-tiles (the subject sits in the middle columns: a fixed
+            // column per XCD would leave the XCDs of the outer columns idle early)
+            const long long g = slot / swz, xr = t.blocked ? ((x + g) & 7) : x;
+            bs = g * (8 * swz) + xr * swz + (slot % swz);
+        }
+    }
+    return bs * nwaves + wave;
+}
+
+struct P3dTileXY { long long n, tx, ty; };  // view, tile column and row on its screen
+
+// where tile `tile` of a tiled launch (tiles_x tiles per screen row) lies
+P3D_HD P3dTileXY p3d_tile_screen(const P3dTileOrder& t, long long tile, int tiles_x, long long tiles_per_img) {
+    P3dTileXY o;
+    o.n = tile / tiles_per_img;
+    const long long tl = tile - o.n * tiles_per_img;
+    o.ty = tl / tiles_x;
+    o.tx = tl - o.ty * tiles_x;
+    if (t.pieces) {
+        // consecutive tiles fill one piece, row by row, before the next piece starts; the pieces of a view in row-major order
+        const long long pc = tl / (t.pw * t.ph);
+        const int q = (int)(tl - pc * (t.pw * t.ph)), PC = tiles_x / t.pw;
+        o.tx = (pc % PC) * t.pw + (q % t.pw);
+        o.ty = (pc / PC) * t.ph + (q / t.pw);
+    } else if (t.blocked) {
+        // Blocked tile order (round 5): consecutive tiles fill a SUPER-TILE of 16 x 16 tiles (128 x 64 pixels)
+        // before the next one starts, and the XCD swizzle above hands an XCD whole super-tiles — so the ~256 waves resident on an
+        // XCD march through a compact screen block whose footprint in the three planes (x-extent 1/4, y-extent 1/8 of the image:
+        // ~0.3 + 2.1 + 1.0 MB) fits that XCD's 4 MB L2.  Row-major order gave an XCD four full-width tile rows: the whole xz plane
+        // (8.4 MB) streamed through every L2 (measured round 4: the 25 MB of planes fetched ~5 x per XCD).
+        const long long st = tl >> 8;
+        const int q = (int)(tl & 255), SX = tiles_x >> 4;
+        o.tx = (st % SX) * 16 + (q & 15);
+        o.ty = (st / SX) * 16 + (q >> 4);
+    }
+    return o;
+}
 
 enum class RenderKernel {
     DUMP,       // k_render<NF, true, FAST, false>: every sample decoded, the stages dumped
@@ -46,7 +151,8 @@ struct RenderPlan {
     int nwaves;           // waves per workgroup
     unsigned grid, block;
     size_t lds_bytes;     // dynamic LDS per workgroup
-    int swz, blocked;     // k_render's XCD tile order (see the kernel); 0 for k_render_slots
+    int swz, blocked;     // k_render's XCD tile order as of round 5 (runs of blocks / whole super-tiles); 0 for k_render_slots
+    P3dTileOrder order;   // ... and the order the launch runs in: that one, or the balanced pieces where the shape divides into them
     long long decode_steps_full;  // wave-level decode steps with every sample decoded
 };
 
@@ -149,6 +255,15 @@ static inline RenderPlan p3d_render_plan(int N, int64_t R, int ray_tile_w, const
             pl.blocked = 1;
             pl.swz = 256 / nw;
         }
+        pl.order.swz = pl.swz;
+        pl.order.blocked = pl.blocked;
+#ifndef P3D_TILE_ORDER_PARENT  // (the switch rebuilds the round-5 order everywhere: the A/B of DESIGN.md section 6)
+        // ... or, round 12, small pieces dealt to the XCDs by a rule of the piece's column and row (p3d_piece_order), where the
+        // shape allows: the early-outs make the tiles uneven, nothing moves work between XCDs, and the sums of many small pieces
+        // per XCD differ less than the sums of 4 super-tiles (modelled: profiles/r12_xcd_model.txt; measured, the time each XCD's last
+        // wave ends: profiles/r12_xcd_finish_*.txt).  Shapes it cannot take (384^2: 96 tile rows are 12 piece rows) keep the above.
+        if (pl.blocked) p3d_piece_order(pl.order, pl.tiles_x, tiles_y, nw, P3D_PIECE_W, P3D_PIECE_H, P3D_XCD_RULE_A, P3D_XCD_RULE_S);
+#endif
     }
     if (lds(nw) > P3D_RENDER_LDS_CU) { pl.err = P3D_E_RANGE; return pl; }
     pl.nwaves = nw;

@@ -27,23 +27,20 @@ import p3d_testing as T  # noqa: E402
 from oracle import oracle  # noqa: E402
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="surface")
-    ap.add_argument("--stride", type=int, default=4)
-    ap.add_argument("--sc", type=int, default=48)
-    ap.add_argument("--sf", type=int, default=48)
-    a = ap.parse_args()
+def tile_steps(scene="surface", stride=4, Sc=48, Sf=48, res=512, azim=20.0):
+    """The view's tiles (tx, ty) with tx % stride == ty % stride == 0, each rendered as one wave: returns (ty, tx, coarse wave-steps,
+    final wave-steps, decodes of the final pass, fraction of the coarse samples cropped), arrays over those tiles in row-major order."""
     spec = importlib.util.spec_from_file_location("p3d_cameras", os.path.join(ROOT, "panic3d-anime-reconstruction_amd", "cameras.py"))
     cams = importlib.util.module_from_spec(spec)  # (the cameras alone: the package itself would load the HIP library)
     spec.loader.exec_module(cams)
-    planes, raw = T.make_bench_scene(a.scene)
-    res, Sc, Sf = 512, a.sc, a.sf
-    o, d = cams.rays_from_label(cams.camera_label(0.0, 20.0, 1.0, 30.0)[None], res)
+    planes, raw = T.make_bench_scene(scene)
+    o, d = cams.rays_from_label(cams.camera_label(0.0, azim, 1.0, 30.0)[None], res)
     o, d = o.reshape(res, res, 3).numpy(), d.reshape(res, res, 3).numpy()
-    idx = []
-    for ty in range(0, res // 4, a.stride):
-        for tx in range(0, res // 8, a.stride):
+    idx, tys, txs = [], [], []
+    for ty in range(0, res // 4, stride):
+        for tx in range(0, res // 8, stride):
+            tys.append(ty)
+            txs.append(tx)
             for j in range(32):  # k_render's lane order inside an 8x4 tile
                 lx, ly = (j & 1) | ((j >> 1) & 6), ((j >> 1) & 1) | ((j >> 3) & 2)
                 idx.append((ty * 4 + ly, tx * 8 + lx))
@@ -73,9 +70,20 @@ def main():
     known = cropped(tm) | ((perm < Sc) & (sm <= -999))
     need = (transmittance_before(tm, sm) >= 1e-60) & ~known
     n_l = need.sum(axis=1).reshape(W, 32)
-    mx, tot = n_l.max(axis=1), n_l.sum(axis=1)
-    S = Sc + Sf
-    print(f"{a.scene} {Sc}+{Sf}, {W} waves ({NR} rays): coarse samples cropped {cropped(tc).mean():.3f}")
+    return np.array(tys), np.array(txs), steps_c, n_l.max(axis=1), n_l.sum(axis=1), float(cropped(tc).mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="surface")
+    ap.add_argument("--stride", type=int, default=4)
+    ap.add_argument("--sc", type=int, default=48)
+    ap.add_argument("--sf", type=int, default=48)
+    a = ap.parse_args()
+    Sc, Sf = a.sc, a.sf
+    _, _, steps_c, mx, tot, crop = tile_steps(a.scene, a.stride, Sc, Sf)
+    W, S = len(mx), Sc + Sf
+    print(f"{a.scene} {Sc}+{Sf}, {W} waves ({W * 32} rays): coarse samples cropped {crop:.3f}")
     print(f"coarse wave-steps {steps_c.mean():.1f} of {Sc}; final wave-steps {mx.mean():.1f} of {S}; "
           f"total {(steps_c + mx).mean():.1f} of {Sc + S} = {(steps_c + mx).mean() / (Sc + S):.4f}")
     print(f"final pass: lane occupancy {tot.sum() / (mx.sum() * 32):.3f}; perfectly packed {np.ceil(tot / 32).mean():.1f} wave-steps")
