@@ -206,6 +206,13 @@ ENCODER_SIGNATURES = {
     "p3d_encoder_forward_f32": (_I, [C.POINTER(EncLayer), _I, _P, _L, _P, _L, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _P, _Z, _P]),
     "p3d_encoder_workspace_bytes": (_Z, [C.POINTER(EncLayer), _I]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_metrics.h declares (the geometry metrics: point-to-mesh distance)
+METRICS_SIGNATURES = {
+    "p3d_point_mesh_plan": (_I, [_L, _L, _I, C.POINTER(C.c_int64), _I]),
+    "p3d_point_mesh_workspace_bytes": (_Z, [_L, _L]),
+    "p3d_point_mesh_dist2_f32": (_I, [_P, _L, _P, _L, _P, _L, _I, _F, _P, _P, _P, _P, _Z, _P]),
+}
+P3D_PM_NO_CULL, P3D_PM_SLICES_SHIFT, P3D_PM_MAX_SLICES, P3D_PM_QUERY_BLOCK, P3D_PM_FACE_TILE = 1, 8, 256, 128, 64  # include/p3d_metrics.h
 P3D_ENC_KC, P3D_ENC_CUS, P3D_ENC_TILE_64, P3D_ENC_TILE_32, P3D_ENC_MAX_SPLIT, P3D_ENC_RELU = 64, 256, 1, 2, 255, 1  # include/p3d_encoder.h
 P3D_ENC_KIND_CONV, P3D_ENC_KIND_MAXPOOL, P3D_ENC_KIND_PREPARE = 0, 1, 2                                           # include/p3d_encoder.h
 P3D_LPIPS_MAX_K, P3D_LPIPS_MAX_STRIDE, P3D_LPIPS_BWD_MAX_CI = 11, 4, 4  # include/p3d_lpips.h
@@ -234,7 +241,7 @@ def lib():
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
                 + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
-                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()):
+                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

@@ -2386,3 +2386,35 @@ def encoder_forward(prog, img, src=0):
     prog.arena[prog.buf_off[src]:prog.buf_off[src] + img.numel()].copy_(img.reshape(-1))
     _encoder_forward_impl(prog)
     return prog
+
+
+# ---- the geometry metrics (include/p3d_metrics.h) -----------------------------------------------------------------------------------------
+def point_mesh_plan(Q, F, slices=0, cull=True):
+    """p3d_point_mesh_plan: dict(qblocks, ntiles, slices, tiles_per_slice, query_block, face_tile) of a call with these sizes."""
+    out = (C.c_int64 * 6)()
+    flags = (0 if cull else _lib.P3D_PM_NO_CULL) | (int(slices) << _lib.P3D_PM_SLICES_SHIFT)
+    _lib.check(_lib.lib().p3d_point_mesh_plan(int(Q), int(F), flags, out, 6), "p3d_point_mesh_plan")
+    return dict(zip(("qblocks", "ntiles", "slices", "tiles_per_slice", "query_block", "face_tile"), (int(x) for x in out)))
+
+
+def point_mesh_dist2(points, verts, faces, cull=False, cull_margin=0.0, slices=0, want_face=True, want_closest=True):
+    """p3d_point_mesh_dist2_f32: (dist2 [Q], face [Q] int32 or None, closest [Q,3] or None) of points [Q,3] against the mesh verts [V,3],
+    faces [F,3] int32 — whose indices the CALLER has checked (panic3d_amd.metrics.point_mesh_squared_distance does).  cull: skip far
+    face tiles (bit-identical outputs; wants spatially sorted points and cull_margin = 64 * 2^-24 * D^2); slices: force the number of
+    face slices (0: the plan's)."""
+    points, verts, faces = _chk(points, "points"), _chk(verts, "verts"), _chk(faces, "faces", torch.int32)
+    if points.dim() != 2 or points.shape[1] != 3 or verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("point_mesh_dist2: points [Q,3], verts [V,3], faces [F,3]")
+    Q, V, F = points.shape[0], verts.shape[0], faces.shape[0]
+    L = _lib.lib()
+    dev = points.device
+    ws = _sg_workspace(dev, L.p3d_point_mesh_workspace_bytes(Q, max(F, 1)))
+    d2 = torch.empty((Q,), dtype=torch.float32, device=dev)
+    face = torch.empty((Q,), dtype=torch.int32, device=dev) if want_face else None
+    closest = torch.empty((Q, 3), dtype=torch.float32, device=dev) if want_closest else None
+    flags = (0 if cull else _lib.P3D_PM_NO_CULL) | (int(slices) << _lib.P3D_PM_SLICES_SHIFT)
+    with _on(dev):
+        rc = L.p3d_point_mesh_dist2_f32(_p(points), Q, _p(verts), V, _p(faces), F, flags, float(cull_margin), _p(d2), _p(face), _p(closest),
+                                        _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_point_mesh_dist2_f32")
+    return d2, face, closest

@@ -90,7 +90,7 @@ def density_grid_sharded(G, ws, cond, resolution=256, dst=0, **kw):
     return res
 
 
-def marching_cubes(vol, rgbs, boxwarp, level=0.5, flip0=False, allow_degenerate=False):
+def marching_cubes(vol, rgbs, boxwarp, level=0.5, flip0=False, allow_degenerate=False, as_tensors=False):
     """`_util/eg3d_metrics3d.py:186-210 marching_cubes(vol, rgbs, boxwarp, level)` with the surface extracted on the device.
     vol [n,n,n] (device tensor; numpy is uploaded), rgbs: [>=3,n,n,n] tensor indexed like the reference does
     (`rgbs[:3, a, b, c]` at `verts.astype(int)`), or a callable `rgbs(ijk[V,3] long) -> [V,3]`, or None.
@@ -98,27 +98,29 @@ def marching_cubes(vol, rgbs, boxwarp, level=0.5, flip0=False, allow_degenerate=
     arrays).  The triangulation is this repo's, not Lewiner's: PARITY UNPINNED against skimage (absent here; the
     fixture generator tests/golden/make_golden_mesh.py and tests/test_mcubes_cpu.py::test_triangulation_against_skimage_lewiner are
     ready for a box that has it).  allow_degenerate=False is what the reference
-    passes to skimage (eg3d_metrics3d.py:189-194): zero-area triangles (a grid value exactly on the level) are removed."""
+    passes to skimage (eg3d_metrics3d.py:189-194): zero-area triangles (a grid value exactly on the level) are removed.
+    as_tensors: the dict holds device tensors instead of numpy arrays (nothing is downloaded; metrics.geometry_metrics takes it)."""
     if not torch.is_tensor(vol):
         vol = torch.as_tensor(np.ascontiguousarray(vol, dtype=np.float32)).cuda()
     n = vol.shape[-1]
     verts, faces, normals, values = ops.marching_cubes(vol.contiguous(), level, flip0=flip0, allow_degenerate=allow_degenerate)
     out = {}
+    host = (lambda t: t) if as_tensors else (lambda t: t.cpu().numpy())
     if rgbs is not None:
         ijk = verts.long()  # .astype(int): truncation; coordinates are >= 0
         if callable(rgbs):
             colors = rgbs(ijk)
         else:
             colors = rgbs[:3, ijk[:, 0], ijk[:, 1], ijk[:, 2]].t()
-        out["colors"] = colors.cpu().numpy()
-    out["verts"] = (verts / n * boxwarp - 0.5 * boxwarp).cpu().numpy()
-    out["faces"] = faces.cpu().numpy()
-    out["normals"] = normals.cpu().numpy()
-    out["values"] = values.cpu().numpy()
+        out["colors"] = host(colors)
+    out["verts"] = host(verts / n * boxwarp - 0.5 * boxwarp)
+    out["faces"] = host(faces)
+    out["normals"] = host(normals)
+    out["values"] = host(values)
     return out
 
 
-def mesh(G, ws, cond, resolution=256, level=0.5, triplane_crop=None, cull_clouds=None, planes=None, **synthesis_kwargs):
+def mesh(G, ws, cond, resolution=256, level=0.5, triplane_crop=None, cull_clouds=None, planes=None, as_tensors=False, **synthesis_kwargs):
     """generate.py:97-103 (get_eg3d_volume + marching_cubes) without the volume leaving the GPU: density grid on the fused
     decode kernel, surface extraction on the device, and the 32-channel colour grid of the reference (17 GB at 512^3, of
     which three channels at the vertices' voxels are used) replaced by ONE decode of exactly those voxels."""
@@ -139,4 +141,4 @@ def mesh(G, ws, cond, resolution=256, level=0.5, triplane_crop=None, cull_clouds
         _, rgb = ops.triplane_decode(nhwc, pts.contiguous(), mlp, opts)
         return rgb[0, :, :3]
 
-    return marching_cubes(dens, colors, rk["box_warp"], level=level, flip0=True)
+    return marching_cubes(dens, colors, rk["box_warp"], level=level, flip0=True, as_tensors=as_tensors)
