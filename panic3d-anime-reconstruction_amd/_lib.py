@@ -83,6 +83,17 @@ class EncLayer(C.Structure):
                                          "reserved")] + [("w_off", C.c_int64), ("b_off", C.c_int64)]
 
 
+class RmlineDog(C.Structure):
+    """p3d_rmline_dog (include/p3d_rmline.h)"""
+    _fields_ = [(n, C.c_double) for n in ("t", "sigma", "k", "epsilon", "kernel_factor")] + [("d", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RmlineLayer(C.Structure):
+    """p3d_rmline_layer (include/p3d_rmline.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("Ci", "Co", "act", "plan")] + [("slope", C.c_float), ("reserved", C.c_int32), ("w_off", C.c_int64),
+                                                                          ("b_off", C.c_int64)]
+
+
 P3D_CONV_MMA_F32, P3D_CONV_MMA_F16, P3D_CONV_MMA_F16X2 = 0, 1, 2
 P3D_WLAYOUT_OIK, P3D_WLAYOUT_PLAIN, P3D_WLAYOUT_UP = 0, 1, 2
 
@@ -212,6 +223,21 @@ METRICS_SIGNATURES = {
     "p3d_point_mesh_workspace_bytes": (_Z, [_L, _L]),
     "p3d_point_mesh_dist2_f32": (_I, [_P, _L, _P, _L, _P, _L, _I, _F, _P, _P, _P, _P, _Z, _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_rmline.h declares (the illustration-to-render module: line mask, generator layers, the walk)
+RMLINE_SIGNATURES = {
+    "p3d_rmline_dog_taps": (_I, [C.POINTER(RmlineDog), C.POINTER(C.c_int)]),
+    "p3d_rmline_mask_f32": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(RmlineDog), _P, _P, _P, _P]),
+    "p3d_rmline_conv_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
+    "p3d_rmline_conv_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P]),
+    "p3d_rmline_struct_layout": (_I, [_I, C.POINTER(C.c_size_t), _I]),
+    "p3d_rmline_forward_f32": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(RmlineDog), C.POINTER(RmlineLayer), _I, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P,
+                                    C.POINTER(C.c_int), _P]),
+}
+P3D_RMLINE_MAX_TAPS, P3D_RMLINE_MAX_DILATE, P3D_RMLINE_MAX_C = 33, 8, 64                                       # include/p3d_rmline.h
+P3D_RMLINE_ACT_NONE, P3D_RMLINE_ACT_LEAKY, P3D_RMLINE_ACT_TANH = 0, 1, 2                                       # include/p3d_rmline.h
+P3D_RMLINE_TILE_8, P3D_RMLINE_TILE_4 = 1, 2                                                                    # include/p3d_rmline.h
+P3D_RMLINE_IN_STACK, P3D_RMLINE_OUT_PLANAR, P3D_RMLINE_OUT_LERP, P3D_RMLINE_IN_NO_MASK = 1, 2, 4, 8            # include/p3d_rmline.h
+P3D_RMLINE_FWD_MASK_INPUT, P3D_RMLINE_FWD_LERP = 1, 2                                                          # include/p3d_rmline.h
 P3D_PM_NO_CULL, P3D_PM_SLICES_SHIFT, P3D_PM_MAX_SLICES, P3D_PM_QUERY_BLOCK, P3D_PM_FACE_TILE = 1, 8, 256, 128, 64  # include/p3d_metrics.h
 P3D_ENC_KC, P3D_ENC_CUS, P3D_ENC_TILE_64, P3D_ENC_TILE_32, P3D_ENC_MAX_SPLIT, P3D_ENC_RELU = 64, 256, 1, 2, 255, 1  # include/p3d_encoder.h
 P3D_ENC_KIND_CONV, P3D_ENC_KIND_MAXPOOL, P3D_ENC_KIND_PREPARE = 0, 1, 2                                           # include/p3d_encoder.h
@@ -241,7 +267,7 @@ def lib():
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
                 + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
-                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
+                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(RMLINE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()
@@ -254,6 +280,7 @@ def lib():
 
 OPTIM_STRUCT_MIRRORS = {0: OptimTensor, 1: OptimStep, 2: OptimChunk, 3: OptimArgs}  # P3D_OPTIM_STRUCT_* (p3d_optim_struct_layout)
 STRUCT_MIRRORS = {0: Opts, 1: Dumps, 2: PasteArgs, 3: ConvArgs}  # P3D_STRUCT_* -> the ctypes restatement above
+RMLINE_STRUCT_MIRRORS = {0: RmlineDog, 1: RmlineLayer}  # p3d_rmline_struct_layout
 
 
 def check_struct_layouts(L):
@@ -266,7 +293,8 @@ def check_struct_layouts(L):
         raise RuntimeError(f"EncLayer: the ctypes mirror in _lib.py does not match the struct {SO} was compiled with ({list(buf[:max(n, 0)])}): "
                            "include/p3d_encoder.h and _lib.py have diverged")
     for query, which, cls in [("p3d_struct_layout", w, c) for w, c in STRUCT_MIRRORS.items()] + \
-            [("p3d_optim_struct_layout", w, c) for w, c in OPTIM_STRUCT_MIRRORS.items()]:
+            [("p3d_optim_struct_layout", w, c) for w, c in OPTIM_STRUCT_MIRRORS.items()] + \
+            [("p3d_rmline_struct_layout", w, c) for w, c in RMLINE_STRUCT_MIRRORS.items()]:
         n = getattr(L, query)(which, buf, 64)
         if n <= 0:
             raise RuntimeError(f"{query}({which}) failed: {n}")

@@ -2418,3 +2418,259 @@ def point_mesh_dist2(points, verts, faces, cull=False, cull_margin=0.0, slices=0
                                         _p(ws), ws.numel(), _stream())
     _lib.check(rc, "p3d_point_mesh_dist2_f32")
     return d2, face, closest
+
+
+# ======================================================================================================================
+# The illustration-to-render module (include/p3d_rmline.h): the line mask in one launch, one unpadded 3 x 3 convolution
+# per generator layer, and the walk of mask + layers in one C call.  Inference only.  Three device operators (the _impl functions, which
+# the CPU tests replace by torch stand-ins) and their checked public forms.
+# ======================================================================================================================
+RMLINE_ACTS = {"none": _lib.P3D_RMLINE_ACT_NONE, "leaky": _lib.P3D_RMLINE_ACT_LEAKY, "tanh": _lib.P3D_RMLINE_ACT_TANH}
+RMLINE_DOG = dict(t=1.0, sigma=0.5, k=1.6, epsilon=0.01, kernel_factor=4, d=2)  # rmline_wrapper.py:24-33
+
+
+def rmline_dog_taps(sigma=0.5, k=1.6, kernel_factor=4, **_):
+    """(k0, k1): the taps of the two Gaussians (sketchers_v2.py:72-73).  ValueError above P3D_RMLINE_MAX_TAPS = 33 taps, or for k < 1."""
+    sigma, k, kernel_factor = float(sigma), float(k), float(kernel_factor)
+    if not (sigma > 0 and k > 0 and kernel_factor > 0 and np.isfinite([sigma, k, kernel_factor]).all()):
+        raise ValueError("rmline: sigma, k and kernel_factor are positive and finite")
+    if sigma * k * kernel_factor >= _lib.P3D_RMLINE_MAX_TAPS or sigma * kernel_factor >= _lib.P3D_RMLINE_MAX_TAPS:
+        raise ValueError(f"rmline: more than {_lib.P3D_RMLINE_MAX_TAPS} taps (sigma {sigma}, k {k}, kernel_factor {kernel_factor})")
+    k0, k1 = max(2 * int(sigma * kernel_factor) + 1, 3), max(2 * int(sigma * k * kernel_factor) + 1, 3)
+    if max(k0, k1) > _lib.P3D_RMLINE_MAX_TAPS:
+        raise ValueError(f"rmline: {max(k0, k1)} taps, at most {_lib.P3D_RMLINE_MAX_TAPS} (sigma {sigma}, k {k}, kernel_factor {kernel_factor})")
+    if k1 < k0:
+        raise ValueError(f"rmline: k {k} makes the second blur narrower than the first ({k1} < {k0} taps)")
+    return k0, k1
+
+
+def rmline_dog_params(dog=None):
+    """The detector's parameters as a checked dict: RMLINE_DOG (the wrapper's values) updated by `dog`."""
+    p = dict(RMLINE_DOG)
+    extra = set(dog or {}) - set(p)
+    if extra:
+        raise ValueError(f"rmline: unknown detector parameters {sorted(extra)}")
+    p.update(dog or {})
+    p["d"] = int(p["d"])
+    if not 1 <= p["d"] <= _lib.P3D_RMLINE_MAX_DILATE:
+        raise ValueError(f"rmline: d {p['d']}, 1..{_lib.P3D_RMLINE_MAX_DILATE}")
+    if not np.isfinite([float(p["t"]), float(p["epsilon"])]).all():
+        raise ValueError("rmline: t and epsilon are finite")
+    rmline_dog_taps(**p)
+    return p
+
+
+def _rmline_dog_struct(p):
+    return _lib.RmlineDog(float(p["t"]), float(p["sigma"]), float(p["k"]), float(p["epsilon"]), float(p["kernel_factor"]), int(p["d"]), 0)
+
+
+def _rmline_mask_impl(img, hull, dog, want_response):
+    img = _chk(img, "img")
+    hull = _chk(hull, "hull") if hull is not None else None
+    N, Cc, H, W = img.shape
+    mask = torch.empty((N, 1, H, W), dtype=torch.float32, device=img.device)
+    image = torch.empty((N, 3, H, W), dtype=torch.float32, device=img.device) if Cc == 4 else None
+    resp = torch.empty((N, 1, H, W), dtype=torch.float32, device=img.device) if want_response else None
+    st = _rmline_dog_struct(dog)
+    with _on(img.device):
+        rc = _lib.lib().p3d_rmline_mask_f32(_p(img), N, Cc, H, W, _p(hull), C.byref(st), _p(mask), _p(image), _p(resp), _stream())
+    _lib.check(rc, "p3d_rmline_mask_f32")
+    return mask, image, resp
+
+
+def _rmline_hull_chk(hull, img):
+    if hull is None:
+        return None
+    return _lpips_chk(hull, "hull", (img.shape[0], 1, img.shape[2], img.shape[3]))
+
+
+def rmline_mask(img, hull=None, dog=None, want_response=False):
+    """The line mask in ONE launch (p3d_rmline_mask_f32): img [N,C,H,W], C 1, 3 or 4 (RGBA is composited on white) -> (mask [N,1,H,W] of
+    0 / 1, image, response).  image: the composite [N,3,H,W] for C = 4, img itself for C = 3, None for C = 1.  response: the clipped DoG
+    response when want_response, else None.  hull [N,1,H,W] (non-zero = inside) is cleared from the mask.  dog: overrides of RMLINE_DOG."""
+    img = _lpips_chk(img, "img", ndim=4)
+    if img.shape[1] not in (1, 3, 4):
+        raise ValueError(f"img: shape {tuple(img.shape)}, expected 1, 3 or 4 channels")
+    hull = _rmline_hull_chk(hull, img)
+    mask, image, resp = _rmline_mask_impl(img, hull, rmline_dog_params(dog), bool(want_response))
+    return mask, (image if img.shape[1] == 4 else (img if img.shape[1] == 3 else None)), resp
+
+
+def rmline_conv_plan(Ci, Co, force_plan=0):
+    """The host-side plan of one layer (p3d_rmline_conv_plan, no GPU needed): dict(plan, rows, cot, lds_bytes).  ValueError for sizes or a
+    forced plan the layer refuses."""
+    out = (C.c_int * 3)()
+    rc = _lib.lib().p3d_rmline_conv_plan(int(Ci), int(Co), int(force_plan), out)
+    if rc < 0:
+        raise ValueError(f"rmline_conv_plan: Ci {Ci}, Co {Co} (1..{_lib.P3D_RMLINE_MAX_C}), plan {force_plan} (0 chooses, 1 the 8-row tile, 2 the 4-row tile; "
+                         "the 8-row tile must fit the LDS)")
+    return dict(plan=rc, rows=out[0], cot=out[1], lds_bytes=out[2])
+
+
+def _rmline_conv_impl(x, image, mask, hull, wk, bias, act, slope, pad, flags, plan):
+    wk, bias = _chk(wk, "wk"), _chk(bias, "bias")
+    x, image, mask, hull = (_chk(t, n) if t is not None else None for t, n in ((x, "x"), (image, "image"), (mask, "mask"), (hull, "hull")))
+    _, Ci, Co = wk.shape
+    if x is not None and x.data_ptr() % 16:  # (a view into a larger tensor: the kernel reads channel-last inputs in 16-byte vectors)
+        x = x.clone()
+    if flags & _lib.P3D_RMLINE_IN_STACK:
+        N, Hin, Win = image.shape[0], image.shape[2] + 2 * pad, image.shape[3] + 2 * pad
+    else:
+        N, Hin, Win = x.shape[0], x.shape[1], x.shape[2]
+    shape = (N, Co, Hin - 2, Win - 2) if flags & _lib.P3D_RMLINE_OUT_PLANAR else (N, Hin - 2, Win - 2, Co)
+    out = torch.empty(shape, dtype=torch.float32, device=wk.device)
+    with _on(wk.device):
+        rc = _lib.lib().p3d_rmline_conv_f32(_p(x), _p(image), _p(mask), _p(hull), N, Hin, Win, pad, Ci, _p(wk), _p(bias), Co, act, slope, flags, plan,
+                                            _p(out), _stream())
+    _lib.check(rc, "p3d_rmline_conv_f32")
+    return out
+
+
+def rmline_conv(x, wk, bias, act="none", slope=0.01, stack=None, pad=0, planar=False, lerp=None, plan=0):
+    """One unpadded 3 x 3 convolution with bias and activation (p3d_rmline_conv_f32).  x [N,Hin,Win,Ci] channel-last; wk [9,Ci,Co] =
+    weight.permute(2, 3, 1, 0); bias [Co]; act 'none', 'leaky' (slope) or 'tanh' -> [N,Hin-2,Win-2,Co] channel-last, or [N,Co,Hin-2,Win-2]
+    with planar=True.
+    stack=(image [N,3,H,W], mask [N,1,H,W] or None, hull [N,1,H,W] or None) in place of x (x None): the reference's stackin built in the
+    load, image * (1 - mask) and hull replicate-padded by `pad`.
+    lerp=(image [N,3,Ho,Wo], mask [N,1,Ho,Wo]) with planar=True and Co = 3: the store gives torch.lerp(image, act(z), mask)."""
+    if act not in RMLINE_ACTS:
+        raise ValueError(f"act: one of {sorted(RMLINE_ACTS)}, got {act!r}")
+    wk = _lpips_chk(wk, "wk", ndim=3)
+    Ci, Co = wk.shape[1], wk.shape[2]
+    if wk.shape[0] != 9 or not (1 <= Ci <= _lib.P3D_RMLINE_MAX_C and 1 <= Co <= _lib.P3D_RMLINE_MAX_C):
+        raise ValueError(f"wk: shape {tuple(wk.shape)}, expected (9, Ci, Co) with Ci, Co <= {_lib.P3D_RMLINE_MAX_C}")
+    bias = _lpips_chk(bias, "bias", (Co,))
+    pad, flags = int(pad), 0
+    image = mask = hull = None
+    if stack is not None:
+        if x is not None:
+            raise ValueError("rmline_conv: x or stack, not both")
+        image, mask, hull = stack
+        image = _lpips_chk(image, "image", ndim=4)
+        if image.shape[1] != 3:
+            raise ValueError(f"image: shape {tuple(image.shape)}, expected three channels")
+        mask = _lpips_chk(mask, "mask", (image.shape[0], 1) + tuple(image.shape[2:])) if mask is not None else None
+        hull = _rmline_hull_chk(hull, image)
+        if Ci != 3 + (hull is not None):
+            raise ValueError(f"wk: {Ci} input channels, the stack has {3 + (hull is not None)}")
+        if pad < 0:
+            raise ValueError("pad: not negative")
+        N, Hin, Win = image.shape[0], image.shape[2] + 2 * pad, image.shape[3] + 2 * pad
+        flags |= _lib.P3D_RMLINE_IN_STACK
+    else:
+        x = _lpips_chk(x, "x", ndim=4)
+        if x.shape[3] != Ci:
+            raise ValueError(f"x: shape {tuple(x.shape)}, expected channel-last with {Ci} channels")
+        if pad != 0:
+            raise ValueError("pad: only with stack")
+        N, Hin, Win = x.shape[0], x.shape[1], x.shape[2]
+    if Hin < 3 or Win < 3:
+        raise ValueError(f"rmline_conv: a {Hin} x {Win} input is smaller than the filter")
+    if planar:
+        flags |= _lib.P3D_RMLINE_OUT_PLANAR
+    if lerp is not None:
+        if not planar or Co != 3:
+            raise ValueError("lerp: needs planar=True and three output channels")
+        l_image, l_mask = lerp
+        l_image = _lpips_chk(l_image, "lerp image", (N, 3, Hin - 2, Win - 2))
+        l_mask = _lpips_chk(l_mask, "lerp mask", (N, 1, Hin - 2, Win - 2))
+        if stack is not None:
+            if l_image.data_ptr() != image.data_ptr() or (mask is not None and l_mask.data_ptr() != mask.data_ptr()):
+                raise ValueError("lerp: with stack, the same image and mask")
+            if mask is None:
+                flags |= _lib.P3D_RMLINE_IN_NO_MASK
+        image, mask = l_image, l_mask
+        flags |= _lib.P3D_RMLINE_OUT_LERP
+    rmline_conv_plan(Ci, Co, plan)
+    return _rmline_conv_impl(x, image, mask, hull, wk, bias, RMLINE_ACTS[act], float(slope), pad, flags, int(plan))
+
+
+class RmlineProgram:
+    """The generator as p3d_rmline_forward_f32 takes it: the table of layer records and one weight blob.  layers: dicts with wk [9,Ci,Co],
+    bias [Co], act ('none' | 'leaky' | 'tanh'), slope, plan."""
+
+    def __init__(self, layers, device):
+        self.layers, self.device = list(layers), torch.device(device)
+        if not self.layers:
+            raise ValueError("RmlineProgram: at least one layer")
+        self.table = (_lib.RmlineLayer * len(self.layers))()
+        parts, off = [], 0
+        for i, (t, l) in enumerate(zip(self.table, self.layers)):
+            _, t.Ci, t.Co = l["wk"].shape
+            if i and t.Ci != self.table[i - 1].Co:
+                raise ValueError(f"RmlineProgram: layer {i} takes {t.Ci} channels, layer {i - 1} gives {self.table[i - 1].Co}")
+            t.act, t.plan, t.slope, t.reserved = RMLINE_ACTS[l.get("act", "none")], int(l.get("plan", 0)), float(l.get("slope", 0.01)), 0
+            rmline_conv_plan(t.Ci, t.Co, t.plan)
+            t.w_off, t.b_off = off, off + l["wk"].numel()
+            parts += [l["wk"].detach().to(torch.float32).reshape(-1), l["bias"].detach().to(torch.float32).reshape(-1)]
+            off += l["wk"].numel() + l["bias"].numel()
+        self.weights = torch.cat(parts).to(self.device).contiguous()
+        self.width = max(t.Co for t in self.table)
+        self._acts = (None, None)
+        self.launches = None  # (set by every run: kernels the call started)
+
+    def acts(self, n):
+        """Two channel-last activation buffers of at least n floats, kept between calls."""
+        if self._acts[0] is None or self._acts[0].numel() < n:
+            self._acts = tuple(torch.empty((max(n, 1),), dtype=torch.float32, device=self.device) for _ in range(2))
+        return self._acts
+
+
+def _rmline_forward_impl(prog, img, hull, dog, mask, pad, flags):
+    img = _chk(img, "img")
+    hull, mask = (_chk(t, n) if t is not None else None for t, n in ((hull, "hull"), (mask, "mask")))
+    _chk(prog.weights, "the program's weights")
+    N, Cc, H, W = img.shape
+    n = len(prog.layers)
+    dev = img.device
+    image = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev) if Cc == 4 else None
+    if dog is not None:
+        mask = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+    out = torch.empty((N, prog.table[n - 1].Co, H + 2 * pad - 2 * n, W + 2 * pad - 2 * n), dtype=torch.float32, device=dev)
+    need = N * (H + 2 * pad - 2) * (W + 2 * pad - 2) * prog.width if n > 1 else 0
+    act0, act1 = prog.acts(need) if n > 1 else (None, None)
+    st = _rmline_dog_struct(dog) if dog is not None else None
+    count = C.c_int(0)
+    with _on(dev):
+        rc = _lib.lib().p3d_rmline_forward_f32(_p(img), N, Cc, H, W, _p(hull), C.byref(st) if st is not None else None, prog.table, n, _p(prog.weights),
+                                               prog.weights.numel(), pad, flags, _p(image), _p(mask), _p(act0), _p(act1),
+                                               act0.numel() if act0 is not None else 0, _p(out), C.byref(count), _stream())
+    _lib.check(rc, "p3d_rmline_forward_f32")
+    prog.launches = count.value
+    return out, mask, (image if Cc == 4 else img)
+
+
+def rmline_forward(prog, img, hull=None, dog=None, mask=None, pad=None, mask_input=True, lerp=False):
+    """The whole module in ONE call into the library (p3d_rmline_forward_f32) -> (out, mask, image).
+    dog given (a dict of overrides of RMLINE_DOG; {} for the wrapper's values): img [N,3|4,H,W] goes through the mask kernel first
+    (len(layers) + 1 launches); `mask` must be None.  dog None: img [N,3,H,W] and the caller's mask [N,1,H,W] (len(layers) launches).
+    The first layer builds stackin from image, mask (if mask_input) and hull (if the first layer takes four channels), replicate-padded by
+    `pad` (default: the depth, so that the output has the input's size); lerp=True stores torch.lerp(image, out, mask), the wrapper's result.
+    prog.launches receives the number of kernels the call started."""
+    if not isinstance(prog, RmlineProgram):
+        raise TypeError("rmline_forward: an RmlineProgram")
+    img = _lpips_chk(img, "img", ndim=4)
+    n = len(prog.layers)
+    pad = n if pad is None else int(pad)
+    if dog is not None:
+        if mask is not None:
+            raise ValueError("rmline_forward: dog or mask, not both")
+        if img.shape[1] not in (3, 4):
+            raise ValueError(f"img: shape {tuple(img.shape)}, expected 3 or 4 channels")
+        dog = rmline_dog_params(dog)
+    else:
+        if img.shape[1] != 3:
+            raise ValueError(f"img: shape {tuple(img.shape)}, expected 3 channels (an RGBA image needs the detector's composite: pass dog)")
+        if mask is None and (mask_input or lerp):
+            raise ValueError("rmline_forward: mask_input and lerp need a mask (or dog)")
+        if mask is not None:
+            mask = _lpips_chk(mask, "mask", (img.shape[0], 1) + tuple(img.shape[2:]))
+    hull = _rmline_hull_chk(hull, img)
+    if prog.table[0].Ci not in (3, 4) or (prog.table[0].Ci == 4 and hull is None):
+        raise ValueError(f"rmline_forward: the first layer takes {prog.table[0].Ci} channels: 3, or 4 with a hull")
+    if pad < 0 or img.shape[2] + 2 * pad - 2 * n < 1 or img.shape[3] + 2 * pad - 2 * n < 1:
+        raise ValueError(f"rmline_forward: a {img.shape[2]} x {img.shape[3]} image padded by {pad} is too small for {n} unpadded layers")
+    if lerp and (pad != n or prog.table[n - 1].Co != 3):
+        raise ValueError("rmline_forward: lerp needs pad == depth and three output channels")
+    flags = (_lib.P3D_RMLINE_FWD_MASK_INPUT if mask_input else 0) | (_lib.P3D_RMLINE_FWD_LERP if lerp else 0)
+    return _rmline_forward_impl(prog, img, hull, dog, mask, pad, flags)

@@ -217,21 +217,34 @@ def run(G, data, out, subset="front", mesh=False, limit=None, device="cuda", see
 TAGGER_CKPT = "./_train/danbooru_tagger/runs/waning_kate_vulcan0001/checkpoints/epoch=0022-val_f2=0.4461-val_loss=0.0766.ckpt"  # katebackbone.py:13-14
 
 
-def prepare(reference, data, limit=None, device="cuda", encoder="reference"):
+def prepare(reference, data, limit=None, device="cuda", encoder="reference", rmline="reference"):
     """Write the prepared layout with the reference's own data backend and pre-processing networks.  Mirrors generate.py:27-47,68-96
     and measure.py:20-27,108-122; run it from the root of the reference repository's environment.
     encoder='hip': resnet_chonk.npy comes from panic3d_amd.ResnetFeatureExtractorPCA (the HIP encoder) reading the same pca.pkl and
-    the tagger's checkpoint — best-effort: neither file was available to check the loaders against."""
+    the tagger's checkpoint — best-effort: neither file was available to check the loaders against.
+    rmline='hip': cond_image_ortho_front.png comes from panic3d_amd.RMLineWrapper (the HIP line remover) reading the reference's
+    rmlineE_rmlineganA_n04 checkpoint — equally best-effort; the reference's wrapper (pytorch_lightning, kornia, skimage) is not imported."""
     os.chdir(reference)
     sys.path[:0] = [reference]
     import _util.util_v1 as uutil
     from _databacks import lustrous_renders_v1 as dklustr
-    from _train.img2img.util import rmline_wrapper
     from _train.danbooru_tagger.helpers.katepca import ResnetFeatureExtractorPCA
     dk = dklustr.DatabackendMinna()
     bns = [f"daredemoE/fandom_align/{bn}/front" for bn in uutil.read_bns("./_data/lustrous/subsets/daredemoE_test.csv")][:limit]
     aligndata = uutil.pload("./_data/lustrous/renders/daredemoE/fandom_align_alignment.pkl")
-    rmline_model = rmline_wrapper.RMLineWrapper(("rmlineE_rmlineganA_n04", 199)).eval().to(device)
+    if rmline == "hip":
+        import panic3d_amd
+        import _util.training_v1 as utraining
+        from PIL import Image
+        rmline_model = panic3d_amd.RMLineWrapper(utraining.infer_module_checkpoint("rmlineE_rmlineganA_n04", 199).ckpt_fn).to(device)
+
+        def apply_M_keypoints(M, kpts):  # rmline_wrapper.py:121-130
+            kpts = kpts[0]
+            return np.concatenate([(M @ np.concatenate([kpts[:, :2], np.ones((kpts.shape[0], 1))], axis=-1).T).T[:, :2], kpts[:, 2:]], axis=-1)[None, ]
+    else:
+        from _train.img2img.util import rmline_wrapper
+        rmline_model = rmline_wrapper.RMLineWrapper(("rmlineE_rmlineganA_n04", 199)).eval().to(device)
+        apply_M_keypoints = rmline_wrapper._apply_M_keypoints
     if encoder == "hip":
         import panic3d_amd
         resnet = panic3d_amd.ResnetFeatureExtractorPCA("./_data/lustrous/preprocessed/minna_resnet_feats_ortho/pca.pkl", 512, num_classes=None)
@@ -243,13 +256,20 @@ def prepare(reference, data, limit=None, device="cuda", encoder="reference"):
         x = dk[bn]
         with torch.no_grad():
             feats = resnet(x.image)
-            kp = rmline_wrapper._apply_M_keypoints(aligndata[bn]["transformation"], aligndata[bn]["_alignment"]["source"]["keypoints"][
+            kp = apply_M_keypoints(aligndata[bn]["transformation"], aligndata[bn]["_alignment"]["source"]["keypoints"][
                 aligndata[bn]["_alignment"]["source"]["_detection_used"]][None, ])[0, :, :2]
-            img = rmline_model(x.image, kp)
+            if rmline == "hip":
+                out = rmline_model(x.image.convert("RGBA").t().float().to(device), kp)  # [4,H,W]: the alpha passes through
+                front = (out[:3] * out[3:] + (1 - out[3:])).clamp(0, 1).permute(1, 2, 0).cpu().numpy()  # .bg('w').convert('RGB')
+            else:
+                img = rmline_model(x.image, kp)
         name = bn.split("/")[2]
         d = os.path.join(data, name)
         os.makedirs(d, exist_ok=True)
-        img.bg("w").convert("RGB").save(os.path.join(d, "cond_image_ortho_front.png"))
+        if rmline == "hip":
+            Image.fromarray((front * 255).round().astype(np.uint8)).save(os.path.join(d, "cond_image_ortho_front.png"))
+        else:
+            img.bg("w").convert("RGB").save(os.path.join(d, "cond_image_ortho_front.png"))
         np.save(os.path.join(d, "resnet_chonk.npy"), feats[0].float().cpu().numpy())
         for view in ("front", "back"):
             dk[bn.replace("fandom_align", "ortho").replace("/front", "/" + view)].image.convert("RGBA").save(os.path.join(d, f"gt_{view}.png"))
@@ -270,6 +290,8 @@ def main(argv=None):
     pr.add_argument("--limit", type=int)
     pr.add_argument("--encoder", choices=("reference", "hip"), default="reference",
                     help="hip: the conditioning features from panic3d_amd's HIP encoder instead of the reference's torchvision module (unchecked loaders)")
+    pr.add_argument("--rmline", choices=("reference", "hip"), default="reference",
+                    help="hip: the line-removed illustration from panic3d_amd's HIP module instead of the reference's wrapper (unchecked loader)")
     rn = sub.add_parser("run")
     rn.add_argument("--network", required=True)
     rn.add_argument("--reference", required=True, help="root of the reference repository (unpickling needs dnnlib / legacy / torch_utils)")
@@ -281,7 +303,7 @@ def main(argv=None):
     rn.add_argument("--exact", action="store_true", help="exact-contract final pass (default: the renderer's tolerance mode)")
     a = ap.parse_args(argv)
     if a.cmd == "prepare":
-        print(json.dumps({"prepared": len(prepare(os.path.abspath(a.reference), os.path.abspath(a.data), a.limit, encoder=a.encoder))}))
+        print(json.dumps({"prepared": len(prepare(os.path.abspath(a.reference), os.path.abspath(a.data), a.limit, encoder=a.encoder, rmline=a.rmline))}))
         return
     if not torch.cuda.is_available():
         raise SystemExit("eval_front run needs an MI355X: the HIP path has no CPU fallback")

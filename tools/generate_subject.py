@@ -4,7 +4,9 @@ random-init weights and a synthetic illustration (the checkpoint and the AnimeRe
 density grid 256^3 (get_eg3d_volume), then 4 orthographic + 12 perspective views through G.f with the front-view paste.
 Prints a timing breakdown (one JSON line).  --encoder hip: resnet_chonk comes from panic3d_amd.ResnetFeatureExtractorPCA run on the
 synthetic illustration (seeded weights and a seeded orthonormal PCA: the tagger's checkpoint is not here either) instead of torch.randn, and
-the line gains encoder_ms, the extractor's call for one subject."""
+the line gains encoder_ms, the extractor's call for one subject.  --rmline hip: the synthetic illustration (with drawn strokes and an
+alpha channel) passes through panic3d_amd.RMLineWrapper (seeded weights: the released checkpoint is not here, and no landmarks, so an
+empty face hull) before it becomes image_ortho_front, and the line gains rmline_ms, the wrapper's call for one subject."""
 import os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -50,6 +52,22 @@ if "--encoder" in sys.argv:
     torch.cuda.synchronize()
     encoder_ms = (time.perf_counter() - te) * 1e3
     cond["resnet_chonk"] = chonk[None, 0]  # generate.py:92
+rmline_ms = None
+if "--rmline" in sys.argv:
+    if sys.argv[sys.argv.index("--rmline") + 1] != "hip":
+        raise SystemExit("--rmline: 'hip' (the default feeds the raw illustration)")
+    illus = torch.cat([cond["image_ortho_front"][0], torch.ones(1, 512, 512, device=dev)])  # RGBA
+    illus[:3, 100:104, 60:450] = 0.05  # drawn strokes
+    illus[:3, 60:450, 300:303] = 0.05
+    illus[3, :16] = 0.0                # a transparent margin
+    wrap = P.RMLineWrapper().to(dev)
+    wrap(illus)  # warm-up
+    torch.cuda.synchronize()
+    te = time.perf_counter()
+    clean = wrap(illus)  # [4,512,512]: lines removed, the alpha passed through
+    torch.cuda.synchronize()
+    rmline_ms = (time.perf_counter() - te) * 1e3
+    cond["image_ortho_front"] = (clean[:3] * clean[3:] + (1 - clean[3:]))[None].contiguous()  # .bg('w').convert('RGB'), generate.py:91
 opts = {"triplane_crop": 0.1, "cull_clouds": 0.5,
         "paste_params": {"mode": "default", "thresh_weight": 0.95, "thresh_edges": 0.02, "thresh_occ": 0.05, "offset_occ": 0.01,
                          "thresh_dxyz": 0.000005}}
@@ -125,4 +143,5 @@ print(json.dumps({"one_view_f_ms": (t1 - t0) * 1e3, "density_grid_256_ms": (t2 -
                   "views_with_paste_ms": (t3 - tm1) * 1e3, "ms_per_view": (t3 - tm1) * 1e3 / len(views), "ms_per_view_next_subjects": (t3b - t3) * 1e3 / len(views),
                   "subject_total_ms": (t3 - t0 - (tm0 - t2)) * 1e3, "ms_per_view_planes_cached": (t4 - t3) * 1e3 / len(views), "ms_per_view_all_views_one_call": (t6 - t5) * 1e3 / len(views),
                   "ms_per_view_all_views_one_call_sr_f16_operands": (t8 - t7) * 1e3 / len(views), "sr_f16_vs_fp32_psnr_db": sr_f16_psnr, "mean_alpha_last_view": float(o["image_weights"].mean()),
-                  "paste_mask_mean_last_view": float(o["paste"]["mask"].mean()), **({"encoder_ms": encoder_ms} if encoder_ms is not None else {})}))
+                  "paste_mask_mean_last_view": float(o["paste"]["mask"].mean()), **({"encoder_ms": encoder_ms} if encoder_ms is not None else {}),
+                  **({"rmline_ms": rmline_ms} if rmline_ms is not None else {})}))
