@@ -4,9 +4,11 @@ Import name: `panic3d_amd` (see the shim panic3d_amd.py at the repository root; 
 Layout: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), ops.py (tensor-level operators),
 renderer.py (mirror of the reference's ImportanceRenderer call surface), optim.py (the optimiser step and the G_ema update), lpips.py (the AlexNet perceptual distance),
 encoder.py (the conditioning encoder: ResNet-50 features and their PCA), metrics.py (the geometry metrics: point-to-mesh distance, Chamfer, F1),
-rmline.py (the illustration-to-render module: line mask and generator).
+rmline.py (the illustration-to-render module: line mask and generator), clip.py (CLIP's ViT-B/32 image tower and the image similarity).
 """
-from . import _build, _lib, memo, ops, cameras, sharding, stylegan2, generator, volume, outputs, discriminator, loss, optim, lpips, encoder, metrics, rmline  # noqa: F401
+from . import _build, _lib, memo, ops, cameras, sharding, stylegan2, generator, volume, outputs, discriminator, loss, optim, lpips, encoder, metrics, rmline, clip  # noqa: F401
+from .clip import CLIPVisual, CLIPSimilarity  # noqa: F401
+from .metrics import psnr, image_metrics  # noqa: F401
 from .rmline import RMLineGenerator, RMLineWrapper, face_hull  # noqa: F401
 from .renderer import ImportanceRenderer, decoder_params  # noqa: F401
 from .lpips import LPIPS, LPIPSLoss  # noqa: F401

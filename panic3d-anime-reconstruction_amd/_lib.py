@@ -94,6 +94,13 @@ class RmlineLayer(C.Structure):
                                                                           ("b_off", C.c_int64)]
 
 
+class ClipStep(C.Structure):
+    """p3d_clip_step (include/p3d_clip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "M", "K", "Nout", "N", "T", "heads", "S", "patch", "H", "W", "ld", "in_", "out", "res", "flags",
+                                         "plan")] + [("eps", C.c_float), ("reserved", C.c_int32 * 2)] + \
+               [(n, C.c_int64) for n in ("w_off", "b_off", "w2_off", "b2_off")]
+
+
 P3D_CONV_MMA_F32, P3D_CONV_MMA_F16, P3D_CONV_MMA_F16X2 = 0, 1, 2
 P3D_WLAYOUT_OIK, P3D_WLAYOUT_PLAIN, P3D_WLAYOUT_UP = 0, 1, 2
 
@@ -233,6 +240,29 @@ RMLINE_SIGNATURES = {
     "p3d_rmline_forward_f32": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(RmlineDog), C.POINTER(RmlineLayer), _I, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P,
                                     C.POINTER(C.c_int), _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_clip.h declares (CLIP's image tower, its front end, the cosine, PSNR's reductions)
+CLIP_SIGNATURES = {
+    "p3d_clip_resize_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
+    "p3d_clip_resize_table": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int32)]),
+    "p3d_clip_prepare_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "p3d_clip_prepare_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "p3d_clip_gemm_plan": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int)]),
+    "p3d_clip_gemm_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "p3d_clip_gemm_f32": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    "p3d_clip_layernorm_f32": (_I, [_P, _I, _I, _L, _P, _P, _F, _P, _P]),
+    "p3d_clip_embed_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _P]),
+    "p3d_clip_attention_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
+    "p3d_clip_attention_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "p3d_clip_cosine_f32": (_I, [_P, _P, _I, _I, _P, _P]),
+    "p3d_clip_struct_layout": (_I, [C.POINTER(C.c_size_t), _I]),
+    "p3d_clip_forward_f32": (_I, [C.POINTER(ClipStep), _I, _P, _L, _P, _L, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _P, _Z, _P]),
+    "p3d_clip_workspace_bytes": (_Z, [C.POINTER(ClipStep), _I]),
+    "p3d_psnr_workspace_bytes": (_Z, [_L]),
+    "p3d_psnr_f32": (_I, [_P, _P, _L, _P, _P, _Z, _P]),
+}
+P3D_CLIP_KC, P3D_CLIP_CUS, P3D_CLIP_TILE_64, P3D_CLIP_TILE_32, P3D_CLIP_MAX_SPLIT, P3D_CLIP_XCDS = 64, 256, 1, 2, 255, 8   # include/p3d_clip.h
+P3D_CLIP_GELU, P3D_CLIP_PATCH, P3D_CLIP_HEAD_DIM, P3D_CLIP_MAX_T, P3D_CLIP_MAX_SIDE, P3D_CLIP_MAX_S = 1, 2, 64, 64, 16384, 4096  # include/p3d_clip.h
+P3D_CLIP_KIND_PREPARE, P3D_CLIP_KIND_GEMM, P3D_CLIP_KIND_LAYERNORM, P3D_CLIP_KIND_EMBED, P3D_CLIP_KIND_ATTENTION = 0, 1, 2, 3, 4  # include/p3d_clip.h
 P3D_RMLINE_MAX_TAPS, P3D_RMLINE_MAX_DILATE, P3D_RMLINE_MAX_C = 33, 8, 64                                       # include/p3d_rmline.h
 P3D_RMLINE_ACT_NONE, P3D_RMLINE_ACT_LEAKY, P3D_RMLINE_ACT_TANH = 0, 1, 2                                       # include/p3d_rmline.h
 P3D_RMLINE_TILE_8, P3D_RMLINE_TILE_4 = 1, 2                                                                    # include/p3d_rmline.h
@@ -267,7 +297,8 @@ def lib():
         L = C.CDLL(SO)
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
                 + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
-                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(RMLINE_SIGNATURES.items()):
+                + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(RMLINE_SIGNATURES.items()) \
+                + list(CLIP_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()
@@ -292,6 +323,10 @@ def check_struct_layouts(L):
     if n <= 0 or list(buf[:n]) != [C.sizeof(EncLayer)] + [getattr(EncLayer, name).offset for name, _ in EncLayer._fields_]:
         raise RuntimeError(f"EncLayer: the ctypes mirror in _lib.py does not match the struct {SO} was compiled with ({list(buf[:max(n, 0)])}): "
                            "include/p3d_encoder.h and _lib.py have diverged")
+    n = L.p3d_clip_struct_layout(buf, 64)
+    if n <= 0 or list(buf[:n]) != [C.sizeof(ClipStep)] + [getattr(ClipStep, name).offset for name, _ in ClipStep._fields_]:
+        raise RuntimeError(f"ClipStep: the ctypes mirror in _lib.py does not match the struct {SO} was compiled with ({list(buf[:max(n, 0)])}): "
+                           "include/p3d_clip.h and _lib.py have diverged")
     for query, which, cls in [("p3d_struct_layout", w, c) for w, c in STRUCT_MIRRORS.items()] + \
             [("p3d_optim_struct_layout", w, c) for w, c in OPTIM_STRUCT_MIRRORS.items()] + \
             [("p3d_rmline_struct_layout", w, c) for w, c in RMLINE_STRUCT_MIRRORS.items()]:

@@ -155,6 +155,35 @@ def point_mesh_f1(p2s, s2p, thresh):
     return {"precision": pre, "recall": rec, "threshold": thresh, "f1": f1}
 
 
+def psnr(pred, target, data_range=None):
+    """`torchmetrics.PeakSignalNoiseRatio()(pred, target)` (measure.py:45) as a float: ONE value for the whole batch,
+    10 log10(range^2 / mse) with mse = sum (pred - target)^2 / count.  data_range=None (the reference's default-constructed metric):
+    range = max(target) - min(target) — torchmetrics was not available where this was written, so that default is UNCHECKED against the
+    package.  The three reductions come from one pass on the device in binary32 (ops.psnr_sums: one small read); the division and the
+    logarithm are taken here in float64.  Identical images give inf.  A constant target with data_range=None has range 0: the formula is
+    evaluated as torch would evaluate it, -inf (nan when the images are identical as well)."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor) or pred.shape != target.shape:
+        raise ValueError("psnr: two tensors of one shape")
+    if torch.is_grad_enabled() and (pred.requires_grad or target.requires_grad):
+        raise NotImplementedError("psnr is inference only: detach the images or call it under torch.no_grad()")
+    if data_range is not None and not float(data_range) > 0.0:
+        raise ValueError(f"psnr: data_range must be positive, got {data_range}")
+    if pred.numel() == 0 or pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError("psnr: non-empty float32 tensors")
+    ss, lo, hi = (np.float64(v) for v in ops._psnr_sums_impl(pred.detach().contiguous(), target.detach().contiguous()).tolist())
+    rng = np.float64(data_range) if data_range is not None else hi - lo
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(10.0 * np.log10(rng * rng / (ss / np.float64(pred.numel()))))
+
+
+def image_metrics(pred, gt, lpips_model, clip_model):
+    """The 2-D block of measure.py:34-50 for one batch of views: {'lpips', 'psnr', 'clip'} as floats.  pred, gt [N,3,H,W] float32 in
+    [0, 1]; lpips_model a panic3d_amd.LPIPSLoss (called as the reference calls it, on the images as they are), clip_model a
+    panic3d_amd.CLIPSimilarity.  lpips and clip are means over the batch (the reference passes one view at a time)."""
+    with torch.no_grad():
+        return {"lpips": float(lpips_model(pred, gt).double().mean()), "psnr": psnr(pred, gt), "clip": float(clip_model(pred, gt).double().mean())}
+
+
 def geometry_metrics(mesh_pred, mesh_gt, n_sample=10000, thresholds=(0.005, 0.01, 0.05, 0.1, 0.5), generator=None, points_pred=None,
                      points_gt=None):
     """measure.py:186-201 for one subject: p2s = the mean distance from points on the predicted mesh to the ground-truth mesh, s2p the

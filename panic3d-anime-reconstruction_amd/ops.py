@@ -2674,3 +2674,295 @@ def rmline_forward(prog, img, hull=None, dog=None, mask=None, pad=None, mask_inp
         raise ValueError("rmline_forward: lerp needs pad == depth and three output channels")
     flags = (_lib.P3D_RMLINE_FWD_MASK_INPUT if mask_input else 0) | (_lib.P3D_RMLINE_FWD_LERP if lerp else 0)
     return _rmline_forward_impl(prog, img, hull, dog, mask, pad, flags)
+
+
+# ======================================================================================================================
+# CLIP's image tower, its front end, the cosine and PSNR's reductions (include/p3d_clip.h).  Inference only.  The device
+# operators are the _impl functions (which the CPU tests replace by torch stand-ins); the public forms check their arguments first.
+# ======================================================================================================================
+def clip_resize_plan(H, W, S):
+    """p3d_clip_resize_plan (host only): dict(h, w, offy, offx, ksy, ksx, row_lo, row_hi) of clip's Resize(S) + CenterCrop(S) of an H x W image."""
+    out = (C.c_int * 8)()
+    rc = _lib.lib().p3d_clip_resize_plan(int(H), int(W), int(S), out)
+    if rc:
+        _lib.check(rc, "p3d_clip_resize_plan")
+    return dict(zip(("h", "w", "offy", "offx", "ksy", "ksx", "row_lo", "row_hi"), out))
+
+
+def clip_resize_table(n_in, n_out, first, count):
+    """p3d_clip_resize_table (host only): PIL's fixed-point bicubic coefficients of outputs first .. first + count - 1 of one axis
+    n_in -> n_out as an int32 array [count, 2 + ksize]: per output xmin, n, k[0 .. ksize)."""
+    L = _lib.lib()
+    scale = max(n_in / n_out, 1.0)
+    ksize = int(np.ceil(2.0 * scale)) * 2 + 1
+    tab = np.zeros((int(count), 2 + ksize), dtype=np.int32)
+    rc = L.p3d_clip_resize_table(int(n_in), int(n_out), int(first), int(count), ksize, tab.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc:
+        _lib.check(rc, "p3d_clip_resize_table")
+    return tab
+
+
+_CLIP_TABLES, _CLIP_TABLES_MAX = {}, 8
+
+
+def clip_prepare_tables(H, W, S, device):
+    """(plan, tabx, taby): the resize plan and the device copies of the two coefficient tables of the S kept columns / rows, kept per
+    (H, W, S, device) for the eight most recently built."""
+    key = (int(H), int(W), int(S), str(device))
+    if key not in _CLIP_TABLES or not memo.enabled():
+        pl = clip_resize_plan(H, W, S)
+        tabx = torch.from_numpy(clip_resize_table(W, pl["w"], pl["offx"], S)).to(device)
+        taby = torch.from_numpy(clip_resize_table(H, pl["h"], pl["offy"], S)).to(device)
+        _CLIP_TABLES.pop(key, None)
+        while len(_CLIP_TABLES) >= _CLIP_TABLES_MAX:  # the oldest entry goes (an evaluation uses one source size)
+            del _CLIP_TABLES[next(iter(_CLIP_TABLES))]
+        _CLIP_TABLES[key] = (pl, tabx, taby)
+    return _CLIP_TABLES[key]
+
+
+def _clip_prepare_impl(img, S):
+    img = _chk(img, "img")
+    N, Cc, H, W = img.shape
+    _, tabx, taby = clip_prepare_tables(H, W, S, img.device)
+    L = _lib.lib()
+    out = torch.empty((N, 3, S, S), dtype=torch.float32, device=img.device)
+    ws = _sg_workspace(img.device, L.p3d_clip_prepare_workspace_bytes(N, H, W, S))
+    with _on(img.device):
+        rc = L.p3d_clip_prepare_f32(_p(img), N, Cc, H, W, S, _p(tabx), _p(taby), _p(out), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_clip_prepare_f32")
+    return out
+
+
+def clip_prepare(img, S=224):
+    """clip's _transform(S) on the device (p3d_clip_prepare_f32): img [N,C>=3,H,W] -> [N,3,S,S]: quantised to 8 bits, PIL's bicubic resize
+    of the shorter side to S bit for bit, centre crop, normalisation."""
+    img = _lpips_chk(img, "img", ndim=4)
+    if img.shape[1] < 3:
+        raise ValueError(f"img: shape {tuple(img.shape)}, expected at least three channels")
+    return _clip_prepare_impl(img, int(S))
+
+
+def clip_gemm_plan(M, K, Nout, force_plan=0):
+    """The host-side plan of one GEMM (p3d_clip_gemm_plan, no GPU needed): dict(code, tile, split, cps, workgroups, workspace_bytes)."""
+    L = _lib.lib()
+    out = (C.c_int * 4)()
+    code = L.p3d_clip_gemm_plan(int(M), int(K), int(Nout), int(force_plan), out)
+    if code < 0:
+        _lib.check(code, "p3d_clip_gemm_plan")
+    return dict(code=code, tile=out[0], split=out[1], cps=out[2], workgroups=out[3],
+                workspace_bytes=L.p3d_clip_gemm_workspace_bytes(int(M), int(K), int(Nout), int(force_plan)))
+
+
+def _clip_gemm_impl(a, w, bias, res, gelu, patch, force_plan, out=None):
+    a, w = _chk(a, "a"), _chk(w, "w")
+    bias = _chk(bias, "bias") if bias is not None else None
+    res = _chk(res, "res") if res is not None else None
+    K, Nout = w.shape
+    if patch:
+        N, S = a.shape[0], a.shape[2]
+        M, flags = N * (S // patch) ** 2, _lib.P3D_CLIP_PATCH
+    else:
+        N, S, M, flags = 0, 0, a.shape[0], 0
+    if gelu:
+        flags |= _lib.P3D_CLIP_GELU
+    L = _lib.lib()
+    if out is None:
+        out = torch.empty((M, Nout), dtype=torch.float32, device=a.device)
+    ws = _sg_workspace(a.device, L.p3d_clip_gemm_workspace_bytes(M, K, Nout, force_plan))
+    with _on(a.device):
+        rc = L.p3d_clip_gemm_f32(_p(a), M, K, _p(w), Nout, _p(bias), _p(res), flags, N, S, patch, _p(out), force_plan, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_clip_gemm_f32")
+    return out
+
+
+def clip_gemm(a, w, bias=None, res=None, gelu=False, patch=0, force_plan=0, inplace=False):
+    """epi(a @ w) (p3d_clip_gemm_f32): a [M,K], or with patch > 0 an image [N,3,S,S] read as flattened patches (K = 3 patch^2); w [K,Nout];
+    bias [Nout]; gelu: QuickGELU; res [M,Nout] is added last (inplace=True writes the result over res).  force_plan: 0 chooses, else
+    (tile << 8) | split (clip_gemm_plan)."""
+    patch = int(patch)
+    if patch:
+        a = _lpips_chk(a, "a", ndim=4)
+        if patch < 1 or a.shape[1] != 3 or a.shape[2] != a.shape[3] or a.shape[2] % patch:
+            raise ValueError(f"a: shape {tuple(a.shape)}, expected [N,3,S,S] with S a multiple of the patch {patch}")
+        M, K = a.shape[0] * (a.shape[2] // patch) ** 2, 3 * patch * patch
+    else:
+        a = _lpips_chk(a, "a", ndim=2)
+        M, K = a.shape
+    w = _lpips_chk(w, "w", (K, w.shape[1] if isinstance(w, torch.Tensor) and w.ndim == 2 else -1))
+    if bias is not None:
+        bias = _lpips_chk(bias, "bias", (w.shape[1],))
+    if res is not None:
+        res = _lpips_chk(res, "res", (M, w.shape[1]))
+    return _clip_gemm_impl(a, w, bias, res, bool(gelu), patch, int(force_plan), out=res if inplace and res is not None else None)
+
+
+def _clip_layernorm_impl(x, rows, D, ld, gamma, beta, eps):
+    x, gamma, beta = _chk(x, "x"), _chk(gamma, "gamma"), _chk(beta, "beta")
+    y = torch.empty((rows, D), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.lib().p3d_clip_layernorm_f32(_p(x), rows, D, ld, _p(gamma), _p(beta), eps, _p(y), _stream())
+    _lib.check(rc, "p3d_clip_layernorm_f32")
+    return y
+
+
+def clip_layernorm(x, gamma, beta, eps=1e-5, rows=None, ld=None):
+    """LayerNorm of the rows of x [M,D] (p3d_clip_layernorm_f32).  rows / ld: normalise `rows` rows that start every `ld` floats of x's
+    storage instead (ld = T * D with rows = N: the class token of each image)."""
+    x = _lpips_chk(x, "x", ndim=2)
+    D = x.shape[1]
+    gamma, beta = _lpips_chk(gamma, "gamma", (D,)), _lpips_chk(beta, "beta", (D,))
+    rows, ld = (x.shape[0] if rows is None else int(rows)), (D if ld is None else int(ld))
+    if rows < 1 or ld < D or (rows - 1) * ld + D > x.numel():
+        raise ValueError(f"clip_layernorm: {rows} rows every {ld} floats do not fit x {tuple(x.shape)}")
+    return _clip_layernorm_impl(x, rows, D, ld, gamma, beta, float(eps))
+
+
+def _clip_embed_impl(patches, cls, pos, N, gamma, beta, eps):
+    patches, cls, pos, gamma, beta = (_chk(t, n) for t, n in ((patches, "patches"), (cls, "cls"), (pos, "pos"), (gamma, "gamma"), (beta, "beta")))
+    T, D = pos.shape
+    y = torch.empty((N * T, D), dtype=torch.float32, device=pos.device)
+    with _on(pos.device):
+        rc = _lib.lib().p3d_clip_embed_f32(_p(patches), _p(cls), _p(pos), N, T, D, _p(gamma), _p(beta), eps, _p(y), _stream())
+    _lib.check(rc, "p3d_clip_embed_f32")
+    return y
+
+
+def clip_embed(patches, cls, pos, gamma, beta, eps=1e-5):
+    """The embedding step (p3d_clip_embed_f32): patches [N (T-1), D] (the patch GEMM's rows), cls [D], pos [T,D] -> ln_pre of
+    [cls | patches] + pos, [N T, D]."""
+    pos = _lpips_chk(pos, "pos", ndim=2)
+    T, D = pos.shape
+    patches = _lpips_chk(patches, "patches", ndim=2)
+    if T < 2 or patches.shape[1] != D or patches.shape[0] % (T - 1):
+        raise ValueError(f"patches: shape {tuple(patches.shape)}, expected [N * {T - 1}, {D}]")
+    cls, gamma, beta = _lpips_chk(cls, "cls", (D,)), _lpips_chk(gamma, "gamma", (D,)), _lpips_chk(beta, "beta", (D,))
+    return _clip_embed_impl(patches, cls, pos, patches.shape[0] // (T - 1), gamma, beta, float(eps))
+
+
+def clip_attention_plan(N, T, heads):
+    """p3d_clip_attention_plan: dict(workgroups, qblocks, rows, lds_bytes)."""
+    out = (C.c_int * 4)()
+    rc = _lib.lib().p3d_clip_attention_plan(int(N), int(T), int(heads), out)
+    if rc:
+        _lib.check(rc, "p3d_clip_attention_plan")
+    return dict(zip(("workgroups", "qblocks", "rows", "lds_bytes"), out))
+
+
+def _clip_attention_impl(qkv, N, T, heads):
+    qkv = _chk(qkv, "qkv")
+    D = qkv.shape[1] // 3
+    out = torch.empty((N * T, D), dtype=torch.float32, device=qkv.device)
+    with _on(qkv.device):
+        rc = _lib.lib().p3d_clip_attention_f32(_p(qkv), N, T, heads, D, _p(out), _stream())
+    _lib.check(rc, "p3d_clip_attention_f32")
+    return out
+
+
+def clip_attention(qkv, N, T, heads):
+    """Softmax attention (p3d_clip_attention_f32): qkv [N T, 3 D], columns q | k | v, head h the columns 64 h .. 64 h + 63 of each ->
+    [N T, D].  D = 64 heads and T <= 64."""
+    N, T, heads = int(N), int(T), int(heads)
+    qkv = _lpips_chk(qkv, "qkv", ndim=2)
+    if N < 1 or T < 1 or heads < 1 or qkv.shape[0] != N * T or qkv.shape[1] % 3:
+        raise ValueError(f"qkv: shape {tuple(qkv.shape)}, expected [{N} * {T}, 3 D]")
+    if qkv.shape[1] != 3 * 64 * heads or T > _lib.P3D_CLIP_MAX_T:
+        raise ValueError(f"clip_attention: D = {qkv.shape[1] // 3} must be 64 * heads ({heads}) and T = {T} at most {_lib.P3D_CLIP_MAX_T}")
+    return _clip_attention_impl(qkv, N, T, heads)
+
+
+def _clip_cosine_impl(a, b):
+    a, b = _chk(a, "a"), _chk(b, "b")
+    sim = torch.empty((a.shape[0],), dtype=torch.float32, device=a.device)
+    with _on(a.device):
+        rc = _lib.lib().p3d_clip_cosine_f32(_p(a), _p(b), a.shape[0], a.shape[1], _p(sim), _stream())
+    _lib.check(rc, "p3d_clip_cosine_f32")
+    return sim
+
+
+def clip_cosine(a, b):
+    """measure.py:42 per pair (p3d_clip_cosine_f32): a, b [pairs, D] -> [pairs], row i of a against row i of b."""
+    a = _lpips_chk(a, "a", ndim=2)
+    b = _lpips_chk(b, "b", tuple(a.shape))
+    if a.numel() == 0:
+        raise ValueError("clip_cosine: no pairs")
+    return _clip_cosine_impl(a, b)
+
+
+def _psnr_sums_impl(pred, target):
+    pred, target = _chk(pred, "pred"), _chk(target, "target")
+    L = _lib.lib()
+    out = torch.empty((3,), dtype=torch.float32, device=pred.device)
+    ws = _sg_workspace(pred.device, L.p3d_psnr_workspace_bytes(pred.numel()))
+    with _on(pred.device):
+        rc = L.p3d_psnr_f32(_p(pred), _p(target), pred.numel(), _p(out), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_psnr_f32")
+    return out
+
+
+def psnr_sums(pred, target):
+    """PSNR's three reductions in one pass (p3d_psnr_f32): a device tensor [sum (pred - target)^2, min target, max target]."""
+    pred = _chk(pred, "pred")
+    target = _lpips_chk(target, "target", tuple(pred.shape))
+    if pred.numel() == 0:
+        raise ValueError("psnr_sums: empty input")
+    return _psnr_sums_impl(pred, target)
+
+
+class ClipProgram:
+    """A whole image tower as p3d_clip_forward_f32 takes it: the table of step records over ONE weight blob (the caller's: records carry
+    offsets into it) and an activation arena.  records: dicts with kind ('prepare' | 'gemm' | 'layernorm' | 'embed' | 'attention'), src / dst
+    / res (buffer indices, res None), the sizes of the kind, and the offsets w, b (b None: no bias), w2, b2.  buf_len: floats per buffer."""
+    KINDS = {"prepare": _lib.P3D_CLIP_KIND_PREPARE, "gemm": _lib.P3D_CLIP_KIND_GEMM, "layernorm": _lib.P3D_CLIP_KIND_LAYERNORM,
+             "embed": _lib.P3D_CLIP_KIND_EMBED, "attention": _lib.P3D_CLIP_KIND_ATTENTION}
+
+    def __init__(self, records, buf_len, weights):
+        self.records, self.weights, self.device = list(records), weights, weights.device
+        self.table = (_lib.ClipStep * len(self.records))()
+        for t, r in zip(self.table, self.records):
+            t.kind = self.KINDS[r["kind"]]
+            for name in ("M", "K", "Nout", "N", "T", "heads", "S", "patch", "H", "W", "ld", "plan"):
+                setattr(t, name, int(r.get(name, 0)))
+            t.in_, t.out, t.res = r["src"], r["dst"], -1 if r.get("res") is None else r["res"]
+            t.flags = (_lib.P3D_CLIP_GELU if r.get("gelu") else 0) | (_lib.P3D_CLIP_PATCH if r.get("patch") else 0)
+            t.eps = float(r.get("eps", 0.0))
+            t.w_off, t.w2_off, t.b2_off = int(r.get("w", 0)), int(r.get("w2", 0)), int(r.get("b2", 0))
+            t.b_off = (-1 if r["kind"] == "gemm" else 0) if r.get("b") is None else int(r["b"])
+        self.n_bufs = len(buf_len)
+        self.buf_len = (C.c_int64 * self.n_bufs)(*[int(n) for n in buf_len])
+        offs, at = [], 0
+        for n in buf_len:
+            offs.append(at)
+            at += (int(n) + 63) // 64 * 64  # every buffer starts on a 256-byte boundary
+        self.buf_off = (C.c_int64 * self.n_bufs)(*offs)
+        self.arena = torch.empty((max(at, 1),), dtype=torch.float32, device=self.device)
+        self.launches = sum(2 if r["kind"] == "prepare" else 1 for r in self.records)  # (+ one per split-K reduction: see clip.py)
+
+    def buffer(self, b, shape):
+        n = 1
+        for s in shape:
+            n *= int(s)
+        return self.arena[self.buf_off[b]:self.buf_off[b] + n].view(*shape)
+
+
+def _clip_forward_impl(prog):
+    _chk(prog.arena, "the program's arena"), _chk(prog.weights, "the program's weights")
+    L = _lib.lib()
+    ws = _sg_workspace(prog.device, L.p3d_clip_workspace_bytes(prog.table, len(prog.records)))
+    with _on(prog.device):
+        rc = L.p3d_clip_forward_f32(prog.table, len(prog.records), _p(prog.weights), prog.weights.numel(), _p(prog.arena), prog.arena.numel(),
+                                    prog.buf_off, prog.buf_len, prog.n_bufs, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_clip_forward_f32")
+
+
+def clip_forward(prog, x, src=0):
+    """Run a whole ClipProgram in ONE call into the library: x is copied into buffer `src` of the arena, every step is launched on the
+    current stream; the results are read with prog.buffer(index, shape) (views of the arena: clone what has to outlive the next call)."""
+    if not isinstance(prog, ClipProgram):
+        raise TypeError("clip_forward: a ClipProgram")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != prog.arena.device:
+        raise RuntimeError(f"x must be a torch.float32 tensor on {prog.arena.device}")
+    if x.numel() != prog.buf_len[src]:
+        raise ValueError(f"x: {x.numel()} values, the program was built for {prog.buf_len[src]}")
+    prog.arena[prog.buf_off[src]:prog.buf_off[src] + x.numel()].copy_(x.reshape(-1))
+    _clip_forward_impl(prog)
+    return prog
