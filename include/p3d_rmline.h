@@ -69,6 +69,7 @@ int p3d_rmline_conv_plan(int Ci, int Co, int force_plan, int* out3);
 #define P3D_RMLINE_OUT_PLANAR 2  /* the output is [N][Co][Ho][Wo], not channel-last */
 #define P3D_RMLINE_OUT_LERP 4    /* with OUT_PLANAR: out = lerp(image, act(z), mask) */
 #define P3D_RMLINE_IN_NO_MASK 8  /* with IN_STACK: the image is NOT multiplied by 1 - mask although a mask is given (for OUT_LERP) */
+#define P3D_RMLINE_SUM_PER_TAP 32 /* z's sum as nine chains, one per tap over ci from 0, added in tap order: no chain longer than Ci (training; other bits) */
 
 /* One UNPADDED 3 x 3 convolution of an input of Hin x Win pixels: Ho = Hin - 2, Wo = Win - 2 (Hin, Win >= 3) and
  *   z[n][oy][ox][co] = (sum over K = (tap t = 3 ty + tx outer, ci inner) ascending of in[n][oy + ty][ox + tx][ci] wk[t][ci][co]) + bias[co]

@@ -6,10 +6,11 @@ renderer.py (mirror of the reference's ImportanceRenderer call surface), optim.p
 encoder.py (the conditioning encoder: ResNet-50 features and their PCA), metrics.py (the geometry metrics: point-to-mesh distance, Chamfer, F1),
 rmline.py (the illustration-to-render module: line mask and generator), clip.py (CLIP's ViT-B/32 image tower and the image similarity).
 """
-from . import _build, _lib, memo, ops, cameras, sharding, stylegan2, generator, volume, outputs, discriminator, loss, optim, lpips, encoder, metrics, rmline, clip  # noqa: F401
+from . import _build, _lib, memo, ops, cameras, sharding, stylegan2, generator, volume, outputs, discriminator, loss, optim, lpips, encoder, metrics, rmline, clip, rmline_train  # noqa: F401
 from .clip import CLIPVisual, CLIPSimilarity  # noqa: F401
 from .metrics import psnr, image_metrics  # noqa: F401
 from .rmline import RMLineGenerator, RMLineWrapper, face_hull  # noqa: F401
+from .rmline_train import RMLineModel  # noqa: F401
 from .renderer import ImportanceRenderer, decoder_params  # noqa: F401
 from .lpips import LPIPS, LPIPSLoss  # noqa: F401
 from .encoder import ResNetEncoder, ResnetFeatureExtractorPCA  # noqa: F401

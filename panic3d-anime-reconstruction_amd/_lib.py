@@ -240,6 +240,19 @@ RMLINE_SIGNATURES = {
     "p3d_rmline_forward_f32": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(RmlineDog), C.POINTER(RmlineLayer), _I, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P,
                                     C.POINTER(C.c_int), _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_rmline_grad.h declares (the module's training operators)
+RMLINE_GRAD_SIGNATURES = {
+    "p3d_rmline_bn_stats_f32": (_I, [_P, _L, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "p3d_rmline_bn_fold_f32": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P]),
+    "p3d_rmline_conv_dgrad_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _F, _I, _P, _P]),
+    "p3d_rmline_wgrad_plan": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int64)]),
+    "p3d_rmline_conv_wgrad_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "p3d_rmline_bn_coef_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "p3d_rmline_head_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "p3d_rmline_head_grad_f32": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _P, _P]),
+}
+P3D_RMLINE_SUM_PER_TAP = 32  # include/p3d_rmline.h
+P3D_RMLINE_BN_MAX_GROUPS, P3D_RMLINE_BN_ROWS, P3D_RMLINE_WG_MAX_SLICES, P3D_RMLINE_OUT_OIHW = 256, 256, 512, 16    # include/p3d_rmline_grad.h
 # symbol -> (restype, argtypes); every function include/p3d_clip.h declares (CLIP's image tower, its front end, the cosine, PSNR's reductions)
 CLIP_SIGNATURES = {
     "p3d_clip_resize_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
@@ -298,7 +311,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
                 + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
                 + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(RMLINE_SIGNATURES.items()) \
-                + list(CLIP_SIGNATURES.items()):
+                + list(CLIP_SIGNATURES.items()) + list(RMLINE_GRAD_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

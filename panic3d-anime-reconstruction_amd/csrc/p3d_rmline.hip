@@ -17,12 +17,7 @@
 
 #include "../../include/p3d_rmline.h"
 #include "p3d_rmline_plan.hpp"
-
-#define RM_WG 256  // four waves
-#define RM_BATCH 4  // loads a lane has in flight while it stages operands
-
-typedef float rm_f32x4 __attribute__((ext_vector_type(4)));
-typedef float rm_f32x2 __attribute__((ext_vector_type(2)));
+#include "p3d_rmline_tile.hpp"
 
 // ---- the line mask ------------------------------------------------------------------------------------------------------------------
 #define RM_MT_W 32
@@ -58,8 +53,6 @@ __device__ __forceinline__ float rm_grey(const float* p, int64_t plane, int C) {
     if (C == 1) return p[0];
     return (0.299f * rm_colour(p, plane, C, 0) + 0.587f * rm_colour(p, plane, C, 1)) + 0.114f * rm_colour(p, plane, C, 2);
 }
-
-__device__ __forceinline__ int rm_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(RM_WG) void k_rm_mask(RmMask m) {
     __shared__ float G[RM_G_ROWS * RM_G_COLS];       // grey, tile + halo
@@ -171,30 +164,15 @@ extern "C" int p3d_rmline_mask_f32(const float* img, int N, int C, int H, int W,
 }
 
 // ---- one layer ------------------------------------------------------------------------------------------------------------------------
-struct RmConv {
-    const float* x;
-    const float* image;
-    const float* mask;
-    const float* hull;
-    const float* wk;
-    const float* bias;
-    float* out;
-    int Hin, Win, Ho, Wo, pad, Ci, Co, act, flags;
-    int Hi, Wi;  // the image's size under IN_STACK
-    int ci4, cip, tiles_x;
-    float slope;
-};
-
 __device__ __forceinline__ float rm_act(float v, int act, float slope) {
     if (act == P3D_RMLINE_ACT_LEAKY) return v > 0.f ? v : v * slope;
     if (act == P3D_RMLINE_ACT_TANH) return tanhf(v);
     return v;
 }
 
-// Waves: wave w takes rows w R .. w R + R - 1 of the tile, each 32 pixels = two 16-pixel blocks.  v_mfma_f32_16x16x4_f32 with the
-// weights as A (A[co = l & 15][k = l >> 4]) and the pixels as B (B[k = l >> 4][pixel = l & 15]): D col = l & 15 is the pixel, rows
-// 4 (l >> 4) + r are four consecutive output channels — one 16-byte store per lane into the channel-last output.
-template <int MB, int R>
+// The patch loads and the tile loop (rm_tile_mma, on __builtin_amdgcn_mfma_f32_16x16x4f32) are p3d_rmline_tile.hpp's, shared with the
+// backward kernels of p3d_rmline_grad.hip.
+template <int MB, int R, bool PT>
 __global__ __launch_bounds__(RM_WG) void k_rm_conv(RmConv c) {
     constexpr int COT = 16 * MB, PH = 4 * R + 2, NB = 2 * R;
     extern __shared__ __attribute__((aligned(16))) float rm_lds[];
@@ -227,88 +205,16 @@ __global__ __launch_bounds__(RM_WG) void k_rm_conv(RmConv c) {
             }
     }
     // the patch: pixels outside the input (a ragged tile) are zeros; they only feed outputs that are not stored
-    if (c.flags & P3D_RMLINE_IN_STACK) {
-        const int64_t plane = (int64_t)c.Hi * c.Wi;
-        for (int i = tid; i < PH * RM_PW; i += RM_WG) {
-            const int py = i / RM_PW, px = i % RM_PW;
-            const int cy = rm_clamp(y0 + py - c.pad, c.Hi - 1), cx = rm_clamp(x0 + px - c.pad, c.Wi - 1);
-            const int64_t at = (int64_t)cy * c.Wi + cx;
-            const float* p = c.image + (int64_t)n * 3 * plane + at;
-            float v0 = p[0], v1 = p[plane], v2 = p[2 * plane];
-            if (c.mask && !(c.flags & P3D_RMLINE_IN_NO_MASK)) {
-                const float s = 1.f - c.mask[(int64_t)n * plane + at];
-                v0 = v0 * s, v1 = v1 * s, v2 = v2 * s;
-            }
-            const float v3 = c.hull ? c.hull[(int64_t)n * plane + at] : 0.f;
-            *(rm_f32x2*)(Xs + i * c.cip) = rm_f32x2{v0, v1};
-            *(rm_f32x2*)(Xs + i * c.cip + 2) = rm_f32x2{v2, v3};
-        }
-    } else {
-        const int nvec = c.ci4 / 4, total = PH * RM_PW * nvec;
-        const bool vec = (c.Ci & 3) == 0;
-        for (int base = tid; base < total; base += RM_BATCH * RM_WG) {
-            rm_f32x4 r[RM_BATCH];
-#pragma unroll
-            for (int j = 0; j < RM_BATCH; ++j) {
-                const int i = base + j * RM_WG, v = i % nvec, pix = i / nvec, gy = y0 + pix / RM_PW, gx = x0 + pix % RM_PW;
-                const bool in = i < total && gy < c.Hin && gx < c.Win;
-                const int64_t at = in ? (((int64_t)n * c.Hin + gy) * c.Win + gx) * c.Ci + 4 * v : 0;
-                if (vec) r[j] = *(const rm_f32x4*)(c.x + at);
-                else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) r[j][e] = c.x[in && 4 * v + e < c.Ci ? at + e : 0];
-            }
-#pragma unroll
-            for (int j = 0; j < RM_BATCH; ++j) {
-                const int i = base + j * RM_WG, v = i % nvec, pix = i / nvec, gy = y0 + pix / RM_PW, gx = x0 + pix % RM_PW;
-                if (i >= total) continue;
-                const bool in = gy < c.Hin && gx < c.Win;
-                float val[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) val[e] = in && 4 * v + e < c.Ci ? r[j][e] : 0.f;
-                *(rm_f32x2*)(Xs + pix * c.cip + 4 * v) = rm_f32x2{val[0], val[1]};
-                *(rm_f32x2*)(Xs + pix * c.cip + 4 * v + 2) = rm_f32x2{val[2], val[3]};
-            }
-        }
-    }
+    if (c.flags & P3D_RMLINE_IN_STACK) rm_stage_stack(c, n, y0, x0, PH, Xs, c.cip, 4);
+    else rm_stage_cl(c, n, y0, x0, 0, PH, Xs, c.cip, c.ci4);
     __syncthreads();
     rm_f32x4 acc[MB][NB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = rm_f32x4{0.f, 0.f, 0.f, 0.f};
+    rm_tile_mma<MB, R, PT>(Xs, Ws, c.cip, c.ci4, wave, lane, acc);  // PT: P3D_RMLINE_SUM_PER_TAP
     const int l15 = lane & 15, kq = lane >> 4;
-    const float* wbase = Ws + l15 * c.cip + kq;
-    const float* xbase = Xs + (wave * R * RM_PW + l15) * c.cip + kq;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const int ty = tap / 3, tx = tap % 3;
-        auto load = [&](int c4, float* a, float* b) {
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb) a[mb] = wbase[(tap * COT + 16 * mb) * c.cip + c4];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) b[nb] = xbase[((nb / 2 + ty) * RM_PW + 16 * (nb % 2) + tx) * c.cip + c4];
-        };
-        auto step = [&](const float* a, const float* b) {
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb], b[nb], acc[mb][nb], 0, 0, 0);
-        };
-        // two k-steps at a time: the second one's LDS reads are issued before the first one's MFMAs (the same k order)
-        float a0[MB], b0[NB], a1[MB], b1[NB];
-        int c4 = 0;
-        for (; c4 + 4 < c.ci4; c4 += 8) {
-            load(c4, a0, b0);
-            load(c4 + 4, a1, b1);
-            step(a0, b0);
-            step(a1, b1);
-        }
-        if (c4 < c.ci4) {
-            load(c4, a0, b0);
-            step(a0, b0);
-        }
-    }
     const bool planar = (c.flags & P3D_RMLINE_OUT_PLANAR) != 0, lerp = (c.flags & P3D_RMLINE_OUT_LERP) != 0;
     const int64_t oplane = (int64_t)c.Ho * c.Wo;
 #pragma unroll
@@ -348,9 +254,6 @@ __global__ __launch_bounds__(RM_WG) void k_rm_conv(RmConv c) {
     }
 }
 
-// a channel-last tensor whose channel count is a multiple of 4 is read and written in 16-byte vectors
-static inline bool rm_misaligned(const void* p, int channels) { return p && (channels & 3) == 0 && ((uintptr_t)p & 15) != 0; }
-
 extern "C" int p3d_rmline_conv_plan(int Ci, int Co, int force_plan, int* out3) {
     RmPlan p;
     const int rc = rm_conv_plan(Ci, Co, force_plan, &p);
@@ -366,7 +269,7 @@ static int rm_conv_check(int N, int Hin, int Win, int pad, int Ci, int Co, int a
     const bool stack = (flags & P3D_RMLINE_IN_STACK) != 0, lerp = (flags & P3D_RMLINE_OUT_LERP) != 0;
     if (stack ? !has_image : !has_x) return P3D_E_ARG;
     if (lerp && (!has_image || !has_mask)) return P3D_E_ARG;
-    if (flags & ~(P3D_RMLINE_IN_STACK | P3D_RMLINE_OUT_PLANAR | P3D_RMLINE_OUT_LERP | P3D_RMLINE_IN_NO_MASK)) return P3D_E_RANGE;
+    if (flags & ~(P3D_RMLINE_IN_STACK | P3D_RMLINE_OUT_PLANAR | P3D_RMLINE_OUT_LERP | P3D_RMLINE_IN_NO_MASK | P3D_RMLINE_SUM_PER_TAP)) return P3D_E_RANGE;
     if (act != P3D_RMLINE_ACT_NONE && act != P3D_RMLINE_ACT_LEAKY && act != P3D_RMLINE_ACT_TANH) return P3D_E_RANGE;
     if (!isfinite(slope) || pad < 0 || pad > 4096 || Hin < 3 || Win < 3 || N > 65535) return P3D_E_RANGE;
     const int rc = rm_conv_plan(Ci, Co, force_plan, p);
@@ -385,26 +288,14 @@ static int rm_conv_check(int N, int Hin, int Win, int pad, int Ci, int Co, int a
     return 0;
 }
 
-#define RM_MAX_DEVICES 64
-
 static int rm_conv_launch(RmConv& c, const RmPlan& p, int N, hipStream_t s) {
-    static const void* const kernels[4] = {(const void*)k_rm_conv<1, 1>, (const void*)k_rm_conv<1, 2>, (const void*)k_rm_conv<2, 1>,
-                                           (const void*)k_rm_conv<2, 2>};
-    static bool raised[4][RM_MAX_DEVICES];  // the dynamic-LDS limit is a property of (kernel, device): raised once for each
-    const int which = (p.cot == 32 ? 2 : 0) + (p.rows == 8 ? 1 : 0);
-    if (p.lds > 64 * 1024) {  // above the default limit of a launch's dynamic LDS
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-        const bool known = dev >= 0 && dev < RM_MAX_DEVICES;
-        if (!known || !raised[which][dev]) {
-            const hipError_t attr = hipFuncSetAttribute(kernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, RM_LDS_LIMIT);
-            if (attr != hipSuccess) {
-                (void)hipGetLastError();
-                return (int)attr;
-            }
-            if (known) raised[which][dev] = true;
-        }
-    }
+    static const void* const kernels[8] = {(const void*)k_rm_conv<1, 1, false>, (const void*)k_rm_conv<1, 2, false>, (const void*)k_rm_conv<2, 1, false>,
+                                           (const void*)k_rm_conv<2, 2, false>, (const void*)k_rm_conv<1, 1, true>,  (const void*)k_rm_conv<1, 2, true>,
+                                           (const void*)k_rm_conv<2, 1, true>,  (const void*)k_rm_conv<2, 2, true>};
+    static bool raised[8][RM_MAX_DEVICES];  // the dynamic-LDS limit is a property of (kernel, device): raised once for each
+    const int which = (p.cot == 32 ? 2 : 0) + (p.rows == 8 ? 1 : 0) + ((c.flags & P3D_RMLINE_SUM_PER_TAP) ? 4 : 0);
+    const int rc = rm_raise_lds(kernels[which], p.lds, raised[which]);
+    if (rc) return rc;
     const dim3 grid((unsigned)(c.tiles_x * ((c.Ho + p.rows - 1) / p.rows)), (unsigned)p.cblocks, (unsigned)N);
     void* args[] = {&c};
     return (int)hipLaunchKernel(kernels[which], grid, dim3(RM_WG), args, p.lds, s);

@@ -5,6 +5,7 @@ libpanic3d_hip.so.  All tensors must be float32 CUDA(ROCm) tensors; misuse raise
 (TORCH_CHECK -> RuntimeError, torch_utils/ops/bias_act.cpp:39-55).
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -2427,6 +2428,7 @@ def point_mesh_dist2(points, verts, faces, cull=False, cull_margin=0.0, slices=0
 # ======================================================================================================================
 RMLINE_ACTS = {"none": _lib.P3D_RMLINE_ACT_NONE, "leaky": _lib.P3D_RMLINE_ACT_LEAKY, "tanh": _lib.P3D_RMLINE_ACT_TANH}
 RMLINE_DOG = dict(t=1.0, sigma=0.5, k=1.6, epsilon=0.01, kernel_factor=4, d=2)  # rmline_wrapper.py:24-33
+RMLINE_LAUNCHES = [0]  # kernels started by rmline_conv and by the training operators below (tests and the bench read the difference)
 
 
 def rmline_dog_taps(sigma=0.5, k=1.6, kernel_factor=4, **_):
@@ -2523,16 +2525,18 @@ def _rmline_conv_impl(x, image, mask, hull, wk, bias, act, slope, pad, flags, pl
         rc = _lib.lib().p3d_rmline_conv_f32(_p(x), _p(image), _p(mask), _p(hull), N, Hin, Win, pad, Ci, _p(wk), _p(bias), Co, act, slope, flags, plan,
                                             _p(out), _stream())
     _lib.check(rc, "p3d_rmline_conv_f32")
+    RMLINE_LAUNCHES[0] += 1
     return out
 
 
-def rmline_conv(x, wk, bias, act="none", slope=0.01, stack=None, pad=0, planar=False, lerp=None, plan=0):
+def rmline_conv(x, wk, bias, act="none", slope=0.01, stack=None, pad=0, planar=False, lerp=None, plan=0, per_tap=False):
     """One unpadded 3 x 3 convolution with bias and activation (p3d_rmline_conv_f32).  x [N,Hin,Win,Ci] channel-last; wk [9,Ci,Co] =
     weight.permute(2, 3, 1, 0); bias [Co]; act 'none', 'leaky' (slope) or 'tanh' -> [N,Hin-2,Win-2,Co] channel-last, or [N,Co,Hin-2,Win-2]
     with planar=True.
     stack=(image [N,3,H,W], mask [N,1,H,W] or None, hull [N,1,H,W] or None) in place of x (x None): the reference's stackin built in the
     load, image * (1 - mask) and hull replicate-padded by `pad`.
-    lerp=(image [N,3,Ho,Wo], mask [N,1,Ho,Wo]) with planar=True and Co = 3: the store gives torch.lerp(image, act(z), mask)."""
+    lerp=(image [N,3,Ho,Wo], mask [N,1,Ho,Wo]) with planar=True and Co = 3: the store gives torch.lerp(image, act(z), mask).
+    per_tap=True (P3D_RMLINE_SUM_PER_TAP): z's sum as one chain per tap, the nine added in order — shorter chains for training, other bits."""
     if act not in RMLINE_ACTS:
         raise ValueError(f"act: one of {sorted(RMLINE_ACTS)}, got {act!r}")
     wk = _lpips_chk(wk, "wk", ndim=3)
@@ -2581,6 +2585,8 @@ def rmline_conv(x, wk, bias, act="none", slope=0.01, stack=None, pad=0, planar=F
                 flags |= _lib.P3D_RMLINE_IN_NO_MASK
         image, mask = l_image, l_mask
         flags |= _lib.P3D_RMLINE_OUT_LERP
+    if per_tap:
+        flags |= _lib.P3D_RMLINE_SUM_PER_TAP
     rmline_conv_plan(Ci, Co, plan)
     return _rmline_conv_impl(x, image, mask, hull, wk, bias, RMLINE_ACTS[act], float(slope), pad, flags, int(plan))
 
@@ -2966,3 +2972,359 @@ def clip_forward(prog, x, src=0):
     prog.arena[prog.buf_off[src]:prog.buf_off[src] + x.numel()].copy_(x.reshape(-1))
     _clip_forward_impl(prog)
     return prog
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# The illustration-to-render module's TRAINING operators (include/p3d_rmline_grad.h): batch statistics, the device-side
+# fold of a train-mode batch norm, the data gradient, the weight / bias gradient, the batch norm's backward coefficients and the head;
+# and the two autograd Functions that rmline_train.RMLineModel composes them with.  binary32, fixed sum orders, no atomics, no host sync.
+_RMLINE_WS = {}
+
+
+def _rmline_ws(device, floats):
+    """One float32 workspace per (device, current stream), grown on demand: the launches that share one are ordered on that stream, and
+    operators issued on another stream get a workspace of their own."""
+    with _on(device):
+        key = (device, _raw_stream(_cur_device()))
+    ws = _RMLINE_WS.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _RMLINE_WS[key] = torch.empty(max(int(floats), 1 << 16), dtype=torch.float32, device=device)
+    return ws
+
+
+def _rmline_c(n, name):
+    if not 1 <= n <= _lib.P3D_RMLINE_MAX_C:
+        raise ValueError(f"{name}: {n} channels, 1..{_lib.P3D_RMLINE_MAX_C}")
+    return int(n)
+
+
+def _rmline_aligned(t):
+    return t.clone() if t.data_ptr() % 16 else t  # (a view into a larger tensor: channel-last tensors move in 16-byte vectors)
+
+
+def rmline_bn_stats(x, running_mean=None, running_var=None, counter=None, momentum=0.1):
+    """(mean [C], biased var [C]) of a channel-last activation x [..., C] over all other axes by a centred algorithm
+    (p3d_rmline_bn_stats_f32, two launches).  With running_mean, running_var (float32 [C]) and counter (int64 scalar tensor), all three
+    or none: running <- (1 - momentum) running + momentum batch in place, the variance unbiased, and counter += 1 — torch's
+    BatchNorm2d in train mode.  One value per channel: ValueError, as torch raises, before any launch."""
+    x = _chk(x, "x")
+    if x.ndim < 2:
+        raise ValueError(f"x: shape {tuple(x.shape)}, expected [..., C]")
+    Cc = _rmline_c(x.shape[-1], "x")
+    K = x.numel() // Cc
+    if K <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    given = [t is not None for t in (running_mean, running_var, counter)]
+    if any(given) and not all(given):
+        raise ValueError("rmline_bn_stats: running_mean, running_var and counter come together")
+    if all(given):
+        running_mean, running_var = _lpips_chk(running_mean, "running_mean", (Cc,)), _lpips_chk(running_var, "running_var", (Cc,))
+        counter = _chk(counter, "counter", torch.int64)
+        if counter.numel() != 1:
+            raise ValueError("counter: one int64")
+    if not 0.0 <= float(momentum) <= 1.0:
+        raise ValueError("momentum: 0..1")
+    x = _rmline_aligned(x)
+    mean, var = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
+    ws = _rmline_ws(x.device, _lib.P3D_RMLINE_BN_MAX_GROUPS * 4 * 64)
+    with _on(x.device):
+        rc = _lib.lib().p3d_rmline_bn_stats_f32(_p(x), K, Cc, float(momentum), _p(mean), _p(var), _p(running_mean), _p(running_var), _p(counter),
+                                                _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_rmline_bn_stats_f32")
+    RMLINE_LAUNCHES[0] += 2
+    return mean, var
+
+
+def rmline_bn_fold(w, bias, bn=None):
+    """A layer's operands (wk [9,Ci,Co], bias [Co]) from torch's w [Co,Ci,3,3] and bias, ONE launch (p3d_rmline_bn_fold_f32).
+    bn = (gamma, beta, mean, var, eps) of the batch norm IN FRONT of the convolution folds it in: wk = w s, bias + sum of w (beta - mean s),
+    s = gamma / sqrt(var + eps), in binary32 on the device; None: a re-layout only."""
+    w = _lpips_chk(w, "w", ndim=4)
+    Co, Ci = _rmline_c(w.shape[0], "w"), _rmline_c(w.shape[1], "w")
+    if tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"w: shape {tuple(w.shape)}, expected (Co, Ci, 3, 3)")
+    bias = _lpips_chk(bias, "bias", (Co,))
+    gamma = beta = mean = var = None
+    eps = 0.0
+    if bn is not None:
+        gamma, beta, mean, var, eps = bn
+        gamma, beta, mean, var = (_lpips_chk(t, n, (Ci,)) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var")))
+        if not eps >= 0.0:
+            raise ValueError("eps: not negative")
+    wk, bf = torch.empty((9, Ci, Co), dtype=torch.float32, device=w.device), torch.empty(Co, dtype=torch.float32, device=w.device)
+    with _on(w.device):
+        rc = _lib.lib().p3d_rmline_bn_fold_f32(_p(w), _p(bias), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), Ci, Co, _p(wk), _p(bf), _stream())
+    _lib.check(rc, "p3d_rmline_bn_fold_f32")
+    RMLINE_LAUNCHES[0] += 1
+    return wk, bf
+
+
+def rmline_conv_dgrad(g, wk, a=None, c0=None, c1=None, slope=0.01, planar=False):
+    """The data gradient of one unpadded 3 x 3 layer, ONE launch (p3d_rmline_conv_dgrad_f32): g [N,Hg,Wg,Co] channel-last and the layer's
+    own wk [9,Ci,Co] -> dx [N,Hg+2,Wg+2,Ci] (planar=True: [N,Ci,Hg+2,Wg+2]), the full correlation.  With a [N,Hg+2,Wg+2,Ci] (the
+    post-activation map of the layer below) the store gives (dx + c0 + c1 a) (a > 0 ? 1 : slope): that layer's pre-activation gradient,
+    c0 / c1 [Ci] from rmline_bn_coef (both or neither).  slope <= 0 with a: ValueError."""
+    g = _lpips_chk(g, "g", ndim=4)
+    wk = _lpips_chk(wk, "wk", ndim=3)
+    Ci, Co = _rmline_c(wk.shape[1], "wk"), _rmline_c(wk.shape[2], "wk")
+    if wk.shape[0] != 9 or g.shape[3] != Co:
+        raise ValueError(f"rmline_conv_dgrad: g {tuple(g.shape)} and wk {tuple(wk.shape)} do not fit (g channel-last with Co channels, wk (9, Ci, Co))")
+    N, Hg, Wg = g.shape[:3]
+    if (c0 is None) != (c1 is None) or (c0 is not None and a is None):
+        raise ValueError("rmline_conv_dgrad: c0 and c1 come together, and with a")
+    if a is not None:
+        a = _rmline_aligned(_lpips_chk(a, "a", (N, Hg + 2, Wg + 2, Ci)))
+        if not (slope > 0.0 and math.isfinite(slope)):
+            raise ValueError("slope: positive (the sign of a must be its pre-activation's)")
+        if c0 is not None:
+            c0, c1 = _lpips_chk(c0, "c0", (Ci,)), _lpips_chk(c1, "c1", (Ci,))
+    g = _rmline_aligned(g)
+    out = torch.empty((N, Ci, Hg + 2, Wg + 2) if planar else (N, Hg + 2, Wg + 2, Ci), dtype=torch.float32, device=g.device)
+    with _on(g.device):
+        rc = _lib.lib().p3d_rmline_conv_dgrad_f32(_p(g), N, Hg, Wg, Co, _p(wk), Ci, _p(a), _p(c0), _p(c1), float(slope),
+                                                  _lib.P3D_RMLINE_OUT_PLANAR if planar else 0, _p(out), _stream())
+    _lib.check(rc, "p3d_rmline_conv_dgrad_f32")
+    RMLINE_LAUNCHES[0] += 1
+    return out
+
+
+def rmline_wgrad_plan(N, Ci, Co, force_slices=0):
+    """The host-side plan of a weight gradient (p3d_rmline_wgrad_plan, no GPU needed): dict(slices, sets, lds_bytes, ws_floats).
+    ValueError for sizes the kernel refuses or force_slices outside 1..min(N, 512)."""
+    out = (C.c_int64 * 4)()
+    rc = _lib.lib().p3d_rmline_wgrad_plan(int(N), int(Ci), int(Co), int(force_slices), out)
+    if rc < 0:
+        raise ValueError(f"rmline_wgrad_plan: N {N}, Ci {Ci}, Co {Co} (1..{_lib.P3D_RMLINE_MAX_C}), force_slices {force_slices} "
+                         f"(0 chooses; at most min(N, {_lib.P3D_RMLINE_WG_MAX_SLICES}))")
+    return dict(slices=int(out[0]), sets=int(out[1]), lds_bytes=int(out[2]), ws_floats=int(out[3]))
+
+
+def rmline_conv_wgrad(x, dz, stack=None, pad=0, force_slices=0, oihw=False):
+    """(dw, dbias) of one unpadded 3 x 3 layer, TWO launches (p3d_rmline_conv_wgrad_f32): x [N,Hin,Win,Ci] channel-last (or, with x None,
+    stack=(image, mask or None, hull or None) and pad as rmline_conv builds the first layer's input in the load) and dz [N,Hin-2,Win-2,Co]
+    -> dw [9,Ci,Co] (oihw=True: [Co,Ci,3,3], torch's layout) and dbias [Co].  force_slices: the number of patch slices (0: the plan's)."""
+    dz = _lpips_chk(dz, "dz", ndim=4)
+    Co = _rmline_c(dz.shape[3], "dz")
+    pad, flags = int(pad), _lib.P3D_RMLINE_OUT_OIHW if oihw else 0
+    image = mask = hull = None
+    if stack is not None:
+        if x is not None:
+            raise ValueError("rmline_conv_wgrad: x or stack, not both")
+        image, mask, hull = stack
+        image = _lpips_chk(image, "image", ndim=4)
+        if image.shape[1] != 3 or pad < 0:
+            raise ValueError(f"image: shape {tuple(image.shape)}, expected three channels; pad not negative")
+        mask = _lpips_chk(mask, "mask", (image.shape[0], 1) + tuple(image.shape[2:])) if mask is not None else None
+        hull = _rmline_hull_chk(hull, image)
+        Ci = 3 + (hull is not None)
+        N, Hin, Win = image.shape[0], image.shape[2] + 2 * pad, image.shape[3] + 2 * pad
+        flags |= _lib.P3D_RMLINE_IN_STACK
+    else:
+        x = _rmline_aligned(_lpips_chk(x, "x", ndim=4))
+        Ci = _rmline_c(x.shape[3], "x")
+        if pad != 0:
+            raise ValueError("pad: only with stack")
+        N, Hin, Win = x.shape[:3]
+    if Hin < 3 or Win < 3 or tuple(dz.shape) != (N, Hin - 2, Win - 2, Co):
+        raise ValueError(f"rmline_conv_wgrad: dz {tuple(dz.shape)} for an input of {N} x {Hin} x {Win}")
+    plan = rmline_wgrad_plan(N, Ci, Co, force_slices)
+    dz = _rmline_aligned(dz)
+    dw = torch.empty((Co, Ci, 3, 3) if oihw else (9, Ci, Co), dtype=torch.float32, device=dz.device)
+    db = torch.empty(Co, dtype=torch.float32, device=dz.device)
+    ws = _rmline_ws(dz.device, plan["ws_floats"])
+    with _on(dz.device):
+        rc = _lib.lib().p3d_rmline_conv_wgrad_f32(_p(x), _p(image), _p(mask), _p(hull), N, Hin, Win, pad, Ci, _p(dz), Co, flags, int(force_slices),
+                                                  _p(dw), _p(db), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "p3d_rmline_conv_wgrad_f32")
+    RMLINE_LAUNCHES[0] += 2
+    return dw, db
+
+
+def rmline_bn_coef(dwk_f, db_f, w, gamma, beta, mean, var, eps, K, want_dw=True, want_affine=True):
+    """The backward of the batch norm folded into a layer, ONE launch (p3d_rmline_bn_coef_f32) -> (dgamma, dbeta, dw, c0, c1): from the
+    FOLDED operands' gradients dwk_f [9,Ci,Co], db_f [Co], the raw w [Co,Ci,3,3] and the batch norm's gamma, beta, mean, var [Ci], eps and count
+    K.  dw [Co,Ci,3,3] is the raw weight's gradient; c0, c1 [Ci] are what rmline_conv_dgrad's store adds.  dgamma / dbeta (want_affine)
+    and dw (want_dw) are None when not wanted."""
+    dwk_f = _lpips_chk(dwk_f, "dwk_f", ndim=3)
+    Ci, Co = _rmline_c(dwk_f.shape[1], "dwk_f"), _rmline_c(dwk_f.shape[2], "dwk_f")
+    if dwk_f.shape[0] != 9:
+        raise ValueError(f"dwk_f: shape {tuple(dwk_f.shape)}, expected (9, Ci, Co)")
+    db_f, w = _lpips_chk(db_f, "db_f", (Co,)), _lpips_chk(w, "w", (Co, Ci, 3, 3))
+    gamma, beta, mean, var = (_lpips_chk(t, n, (Ci,)) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var")))
+    if int(K) <= 1 or not eps >= 0.0:
+        raise ValueError("rmline_bn_coef: K > 1 and eps >= 0")
+    dev = w.device
+    dgamma, dbeta = (torch.empty(Ci, dtype=torch.float32, device=dev), torch.empty(Ci, dtype=torch.float32, device=dev)) if want_affine else (None, None)
+    dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=dev) if want_dw else None
+    c0, c1 = torch.empty(Ci, dtype=torch.float32, device=dev), torch.empty(Ci, dtype=torch.float32, device=dev)
+    with _on(dev):
+        rc = _lib.lib().p3d_rmline_bn_coef_f32(_p(dwk_f), _p(db_f), _p(w), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(K), Ci, Co, _p(dgamma), _p(dbeta),
+                                               _p(dw), _p(c0), _p(c1), _stream())
+    _lib.check(rc, "p3d_rmline_bn_coef_f32")
+    RMLINE_LAUNCHES[0] += 1
+    return dgamma, dbeta, dw, c0, c1
+
+
+def rmline_head(t, image, mask, hull=None, crop=0):
+    """The head of the loss, ONE launch (p3d_rmline_head_f32): t, image [N,3,H,W], mask [N,1,H,W] -> (img = torch.lerp(image, t, mask),
+    loss_l1 [N] = mean |img - image|, crop_img, crop_hull).  crop > 0: the centre window of img ([N,3,H-2crop,W-2crop]) and of hull
+    [N,1,H,W] (None: no crop_hull) — the discriminator's input; crop = 0: both None."""
+    t = _lpips_chk(t, "t", ndim=4)
+    N, Cc, H, W = t.shape
+    if Cc != 3:
+        raise ValueError(f"t: shape {tuple(t.shape)}, expected three channels")
+    image, mask = _lpips_chk(image, "image", (N, 3, H, W)), _lpips_chk(mask, "mask", (N, 1, H, W))
+    hull = _rmline_hull_chk(hull, image)
+    crop = int(crop)
+    if crop < 0 or H - 2 * crop < 1 or W - 2 * crop < 1:
+        raise ValueError(f"crop: {crop} of a {H} x {W} map")
+    dev = t.device
+    img, l1 = torch.empty_like(t), torch.empty(N, dtype=torch.float32, device=dev)
+    ci = torch.empty((N, 3, H - 2 * crop, W - 2 * crop), dtype=torch.float32, device=dev) if crop else None
+    ch = torch.empty((N, 1, H - 2 * crop, W - 2 * crop), dtype=torch.float32, device=dev) if crop and hull is not None else None
+    with _on(dev):
+        rc = _lib.lib().p3d_rmline_head_f32(_p(t), _p(image), _p(mask), _p(hull), N, H, W, crop, _p(img), _p(l1), _p(ci), _p(ch), _stream())
+    _lib.check(rc, "p3d_rmline_head_f32")
+    RMLINE_LAUNCHES[0] += 1
+    return img, l1, ci, ch
+
+
+def rmline_head_grad(t, img, image, mask, g_l1, d, crop=0, shape=None):
+    """The head's backward, ONE launch (p3d_rmline_head_grad_f32) -> [N,H,W,3] channel-last:
+    f m (g_l1[n] sign(img - image) / (3 H W) + d inside the centre window), f = 1 - t^2 (t None: 1), m = mask (None: 1).
+    g_l1 [N] or None (no L1 term); d [N,3,H-2crop,W-2crop] in ANY strides, or None.  shape = (N, H, W) when neither t nor img says it."""
+    ref = t if t is not None else (img if img is not None else None)
+    if ref is not None:
+        N, H, W = ref.shape[0], ref.shape[2], ref.shape[3]
+    else:
+        N, H, W = shape
+    crop = int(crop)
+    t = _lpips_chk(t, "t", (N, 3, H, W)) if t is not None else None
+    mask = _lpips_chk(mask, "mask", (N, 1, H, W)) if mask is not None else None
+    if g_l1 is not None:
+        g_l1, img, image = _lpips_chk(g_l1, "g_l1", (N,)), _lpips_chk(img, "img", (N, 3, H, W)), _lpips_chk(image, "image", (N, 3, H, W))
+    ds = None
+    if d is not None:
+        if not d.is_cuda or d.dtype != torch.float32 or tuple(d.shape) != (N, 3, H - 2 * crop, W - 2 * crop):
+            raise ValueError(f"d: a float32 device tensor of shape {(N, 3, H - 2 * crop, W - 2 * crop)}")
+        ds = (C.c_int64 * 4)(*d.stride())
+    out = torch.empty((N, H, W, 3), dtype=torch.float32, device=(t if t is not None else (d if d is not None else img)).device)
+    with _on(out.device):
+        rc = _lib.lib().p3d_rmline_head_grad_f32(_p(t), _p(img if g_l1 is not None else None), _p(image if g_l1 is not None else None), _p(mask),
+                                                 _p(g_l1), _p(d), ds, N, H, W, crop, _p(out), _stream())
+    _lib.check(rc, "p3d_rmline_head_grad_f32")
+    RMLINE_LAUNCHES[0] += 1
+    return out
+
+
+class RmlineStackFunction(torch.autograd.Function):
+    """One pass through a stack of unpadded 3 x 3 convolutions in TRAIN mode — the generator or the discriminator of rmlineganA.py:65-100:
+    LeakyReLU and a batch norm with THIS call's statistics after every convolution but the last.
+
+    apply(spec, image, mask, hull, *params): the first layer reads the stack of image * (1 - mask) and hull built in the load; params =
+    (w_0, b_0, gamma_0, beta_0, w_1, b_1, ..., w_last, b_last); spec = dict(pad, slope, last_act 'tanh' | 'none', planar, bns: the
+    BatchNorm2d modules, whose running statistics and counters are updated in place).  Returns the last layer's output, planar
+    [N,Co,H,W] (spec['planar']) or channel-last.  Each batch norm is folded into the NEXT convolution on the device (rmline_bn_fold),
+    so the forward is rmline_conv's kernel (with per-tap chains); the post-activation map of every layer is kept.
+
+    backward: per layer from the last, wgrad (of the folded operands) -> coefficients (rmline_bn_coef: the batch norm's parameter
+    gradients, the raw weight's, and c0 / c1) -> dgrad, whose store turns the input gradient into the pre-activation gradient of the
+    layer below.  A layer's wgrad also runs when its own parameters want no gradient but a batch norm stands in front of it: that batch
+    norm's backward needs the sums.  Only `image` and the parameters get gradients."""
+
+    @staticmethod
+    def forward(ctx, spec, image, mask, hull, *params):
+        bns, L = spec["bns"], (len(params) + 2) // 4
+        if len(params) != 4 * L - 2 or len(bns) != L - 1:
+            raise ValueError("RmlineStackFunction: params are (w, b, gamma, beta) per layer, without the last layer's batch norm")
+        acts, stats, folded, x = [], [], [], None
+        for l in range(L):
+            w, b = params[4 * l], params[4 * l + 1]
+            bn = None
+            if l > 0:
+                m = bns[l - 1]
+                bn = (params[4 * l - 2].detach(), params[4 * l - 1].detach(), stats[l - 1][0], stats[l - 1][1], float(m.eps))
+            wk, bf = rmline_bn_fold(w.detach(), b.detach(), bn)
+            last = l == L - 1
+            x = rmline_conv(x, wk, bf, act=spec["last_act"] if last else "leaky", slope=spec["slope"], stack=(image, mask, hull) if l == 0 else None,
+                            pad=spec["pad"] if l == 0 else 0, planar=last and spec["planar"], per_tap=True)
+            folded.append(wk)
+            if not last:
+                m = bns[l]
+                if m.momentum is None:
+                    raise NotImplementedError("BatchNorm2d(momentum=None): the cumulative average is not built")
+                track = m.track_running_stats and m.running_mean is not None
+                stats.append(rmline_bn_stats(x, m.running_mean if track else None, m.running_var if track else None,
+                                             m.num_batches_tracked if track else None, float(m.momentum)))
+                acts.append(x)
+        # every tensor through save_for_backward, the output included: an attribute of the ctx would tie the output to its own grad_fn
+        # in a reference cycle and keep a pass's activations alive until the cyclic collector runs
+        ctx.spec, ctx.L = spec, L
+        ctx.save_for_backward(image, mask, hull, x, *params, *folded, *acts, *[m for m, _ in stats], *[v for _, v in stats])
+        return x
+
+    @staticmethod
+    def backward(ctx, dout):
+        spec, L = ctx.spec, ctx.L
+        saved = list(ctx.saved_tensors)
+        image, mask, hull, out = saved[:4]
+        at = [4]
+
+        def take(n):
+            at[0] += n
+            return saved[at[0] - n:at[0]]
+        params, folded, acts = [p.detach() for p in take(4 * L - 2)], take(L), take(L - 1)
+        stats = list(zip(take(L - 1), take(L - 1)))
+        need = ctx.needs_input_grad  # (spec, image, mask, hull, *params)
+        if spec["last_act"] == "tanh":  # (1 - t^2) d, planar -> channel-last, in one launch
+            dz = rmline_head_grad(out, None, None, None, None, dout, 0)
+        else:
+            dz = dout.contiguous() if not spec["planar"] else dout.permute(0, 2, 3, 1).contiguous()
+        grads, dimage = [None] * len(params), None
+        lowest = min([l for l in range(L) if any(need[4 + 4 * l + j] for j in range(4) if 4 * l + j < len(params))] or [L])
+        for l in reversed(range(L)):
+            if l < lowest and not need[1]:
+                break
+            w = params[4 * l]
+            want_w = need[4 + 4 * l] or need[4 + 4 * l + 1]
+            if want_w or l > 0:
+                dw, db = rmline_conv_wgrad(acts[l - 1] if l > 0 else None, dz, stack=(image, mask, hull) if l == 0 else None,
+                                           pad=spec["pad"] if l == 0 else 0, oihw=l == 0)
+            if l > 0:
+                want_affine = need[4 + 4 * l - 2] or need[4 + 4 * l - 1]
+                K = acts[l - 1].numel() // acts[l - 1].shape[-1]
+                dgamma, dbeta, dw, c0, c1 = rmline_bn_coef(dw, db, w, params[4 * l - 2], params[4 * l - 1], stats[l - 1][0], stats[l - 1][1], float(spec["bns"][l - 1].eps), K,
+                                                           want_dw=want_w, want_affine=want_affine)
+                if want_affine:
+                    grads[4 * l - 2], grads[4 * l - 1] = dgamma, dbeta
+                dz = rmline_conv_dgrad(dz, folded[l], a=acts[l - 1], c0=c0, c1=c1, slope=spec["slope"])
+            elif need[1]:
+                dimage = rmline_conv_dgrad(dz, folded[0], planar=True)[:, :3]
+            if want_w:
+                grads[4 * l], grads[4 * l + 1] = dw, db
+        return (None, dimage, None, None) + tuple(g if need[4 + i] else None for i, g in enumerate(grads))
+
+
+class RmlineHeadFunction(torch.autograd.Function):
+    """The head of rmlineganA.loss (rmlineganA.py:178-187): apply(t, image, mask, hull, crop) -> (img, loss_l1 [N], crop_img, crop_hull)
+    as rmline_head gives them.  Gradients reach t only, from loss_l1 and crop_img (img itself is marked non-differentiable: the
+    reference's loss uses it through these two alone); t's gradient is handed over in channel-last memory."""
+
+    @staticmethod
+    def forward(ctx, t, image, mask, hull, crop):
+        img, l1, ci, ch = rmline_head(t.detach(), image, mask, hull, crop)
+        ctx.save_for_backward(img, image, mask)
+        ctx.crop = int(crop)
+        ctx.set_materialize_grads(False)
+        outs = (img, l1, ci, ch)
+        ctx.mark_non_differentiable(*[o for o in (img, ch) if o is not None])
+        return outs
+
+    @staticmethod
+    def backward(ctx, _dimg, g_l1, d_crop, _dhull):
+        img, image, mask = ctx.saved_tensors
+        if g_l1 is None and d_crop is None:
+            return None, None, None, None, None
+        out = rmline_head_grad(None, img, image, mask, g_l1.contiguous() if g_l1 is not None else None, d_crop, ctx.crop,
+                               shape=(img.shape[0], img.shape[2], img.shape[3]))
+        return out.permute(0, 3, 1, 2), None, None, None, None
