@@ -634,6 +634,17 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             ci = 0;  // from here on: coarse samples among the first m merged ones (the fine index is m - ci)
         }
         P3D_PHASE(P3D_PH_MERGE);
+        // EARLY: the walk keeps the current word of each bit row in a register, shifted so that bit 0 is sample m, and goes back to
+        // LDS only when m enters the next word (four LDS round trips per step before, two of them behind the jump loop's exit);
+        // and it carries the previous sample's position from step to step (recomputed only behind a jump, which moves prev_t).
+        // Not the LDS-resident 96-key kernel (per-ray limits, disparity spacing): its exact instantiation sits at 224 + 32 registers,
+        // and the register walk, with or without the carried position, costs it its second wave per SIMD (226 + 32).  It keeps the
+        // walk that reads the words where it uses them.
+        constexpr bool WALK_REGS = EARLY && (NF != 96 || TCG);
+        constexpr bool CARRY_POS = WALK_REGS;
+        uint32_t kw = 0u, sw = 0u;
+        if constexpr (WALK_REGS) { kw = knA[j]; sw = slA[j]; }
+        float ppx = ox + st.prev_t * dx, ppy = oy + st.prev_t * dy, ppz = oz + st.prev_t * dz;
         for (int it = 0;; ++it) {
             bool take_c, known = false;  // known: sigma = -1000 without a decode (reached here only behind a sigma > 602)
             float t;
@@ -649,24 +660,23 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                 // ... and a ray that has taken its last sample is done whatever that sample was: the jump below, which also notices
                 // the end of the list, is not reached behind a sigma > 602 (binarize's solid value as the LAST sample)
                 if (!done && (m >= S || st.Td < (FAST ? P3D_FAST_TD_CUT : 1e-60))) done = true;
-                if (!done && (first || st.prev_sigma <= 602.0f)) {
-                    // jump over the run of known samples that starts at m (one iteration per 32-bit word the run touches)
-                    bool any = false, last_c = false;
-                    while (m < S) {
-                        const int sh = m & 31, left = (32 - sh < S - m) ? 32 - sh : S - m;
-                        const uint32_t kw = knA[(m >> 5) * 32 + j] >> sh, sw = slA[(m >> 5) * 32 + j] >> sh;
-                        int run = (~kw != 0u) ? __builtin_ctz(~kw) : 32;
-                        run = run < left ? run : left;
-                        if (run > 0) {
-                            const uint32_t inrun = run >= 32 ? 0xffffffffu : ((1u << run) - 1u);
-                            ci += __builtin_popcount(sw & inrun);
+                if constexpr (WALK_REGS) {
+                    if (!done && (kw & 1u) != 0u && (first || st.prev_sigma <= 602.0f)) {
+                        // jump over the run of known samples that starts at m (one iteration per 32-bit word the run touches).  The
+                        // words are shifted in from above with zeros, so a run of ones ends at the word's last bit at the latest.
+                        bool last_c = false;
+                        for (;;) {
+                            const int left = S - m;
+                            int run = (~kw != 0u) ? __builtin_ctz(~kw) : 32;
+                            run = run < left ? run : left;
+                            if (run == 0) break;  // (a fresh word only) in front of a sample that has to be decoded
+                            ci += __builtin_popcount(sw & (0xffffffffu >> (32 - run)));
                             last_c = (sw >> (run - 1)) & 1u;
-                            any = true;
                             m += run;
+                            kw >>= (run & 31); sw >>= (run & 31);  // run = 32: the word is used up, see below
+                            if (m >= S || (m & 31) != 0) break;    // the list's end, or a sample that has to be decoded
+                            kw = knA[(m >> 5) * 32 + j]; sw = slA[(m >> 5) * 32 + j];  // the run reached the word's end: on into the next
                         }
-                        if (run < left) break;  // stopped in front of a sample that has to be decoded
-                    }
-                    if (any) {
                         if constexpr (TCG) {
                             // the two coarse depths a jump needs, requested together: the last consumed one and the new head
                             const float pc = tc_sorted(ci > 0 ? ci - 1 : 0);
@@ -676,18 +686,53 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                         st.prev_t = last_c ? tcA[(ci - 1) * 32 + j] : tfA[(m - ci - 1) * 32 + j];
                         st.prev_sigma = P3D_SIGMA_MASKED;
                         prev_skipped = true; first = false;
+                        ppx = ox + st.prev_t * dx; ppy = oy + st.prev_t * dy; ppz = oz + st.prev_t * dz;  // the jump moved prev_t
+                        done = m >= S;
                     }
-                    done = m >= S;
+                    if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
+                    // bit 0 of the two words is sample m.  A finished lane's bits are stale: it needs a valid address and nothing else
+                    take_c = (sw & 1u) != 0u;
+                    known = !done && (kw & 1u) != 0u;
+                } else {
+                    // the walk without the registers (the LDS-resident 96-key kernel): the words are read where they are used
+                    if (!done && (first || st.prev_sigma <= 602.0f)) {
+                        // jump over the run of known samples that starts at m (one iteration per 32-bit word the run touches)
+                        bool any = false, last_c = false;
+                        while (m < S) {
+                            const int sh = m & 31, left = (32 - sh < S - m) ? 32 - sh : S - m;
+                            const uint32_t kr = knA[(m >> 5) * 32 + j] >> sh, sr = slA[(m >> 5) * 32 + j] >> sh;
+                            int run = (~kr != 0u) ? __builtin_ctz(~kr) : 32;
+                            run = run < left ? run : left;
+                            if (run > 0) {
+                                const uint32_t inrun = run >= 32 ? 0xffffffffu : ((1u << run) - 1u);
+                                ci += __builtin_popcount(sr & inrun);
+                                last_c = (sr >> (run - 1)) & 1u;
+                                any = true;
+                                m += run;
+                            }
+                            if (run < left) break;  // stopped in front of a sample that has to be decoded
+                        }
+                        if (any) {
+                            st.prev_t = last_c ? tcA[(ci - 1) * 32 + j] : tfA[(m - ci - 1) * 32 + j];
+                            st.prev_sigma = P3D_SIGMA_MASKED;
+                            prev_skipped = true; first = false;
+                        }
+                        done = m >= S;
+                    }
+                    if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
+                    const int mm = done ? S - 1 : m;  // finished lanes: any valid address
+                    const uint32_t kb = knA[(mm >> 5) * 32 + j] >> (mm & 31), sb = slA[(mm >> 5) * 32 + j] >> (mm & 31);
+                    take_c = (sb & 1u) != 0u;
+                    known = !done && (kb & 1u) != 0u;
                 }
-                if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
-                const int mm = done ? S - 1 : m;  // finished lanes: any valid address
-                const uint32_t kb = knA[(mm >> 5) * 32 + j] >> (mm & 31), sb = slA[(mm >> 5) * 32 + j] >> (mm & 31);
-                take_c = (sb & 1u) != 0u;
-                known = !done && (kb & 1u) != 0u;
                 const int cq = ci < Sc ? ci : Sc - 1, fq = (m - ci < Sf) ? m - ci : (Sf > 0 ? Sf - 1 : 0);
                 if constexpr (TCG) t = take_c ? tcn : tfA[fq * 32 + j];
                 else t = (take_c || Sf == 0) ? tcA[cq * 32 + j] : tfA[fq * 32 + j];
                 if (!done) { ++m; ci += take_c ? 1 : 0; }
+                if constexpr (WALK_REGS) {
+                    kw >>= 1; sw >>= 1;
+                    if (!done && (m & 31) == 0 && m < S) { kw = knA[(m >> 5) * 32 + j]; sw = slA[(m >> 5) * 32 + j]; }  // used one step later: under the decode
+                }
                 if constexpr (TCG) {
                     if (!done && take_c) tcn = tc_sorted(ci < Sc ? ci : Sc - 1);  // used one step later at the earliest: under the decode
                 }
@@ -716,11 +761,14 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             const bool marching = have && !first;
             P3dInterval iv = {0.0f, 0.0f, 0.0f, 0.0f};
             if (marching) iv = p3d_march_interval(st, t, sigma);
-            const float ppx = ox + st.prev_t * dx, ppy = oy + st.prev_t * dy, ppz = oz + st.prev_t * dz;
-            if (early) p3d_guard_colours<FAST>(lds, cx, marching, iv.w, prev_skipped, prev_rgb, ppx, ppy, ppz, skipped, rgb, px, py, pz);
+            if constexpr (!CARRY_POS) { ppx = ox + st.prev_t * dx; ppy = oy + st.prev_t * dy; ppz = oz + st.prev_t * dz; }
+            // one wave-level test in front of the guard's two (k_render_slots<4, ...> spilled 80 more registers with it inside the guard)
+            if (early && (!WALK_REGS || __builtin_amdgcn_ballot_w64(marching && (prev_skipped || skipped) && iv.w != 0.0f) != 0))
+                p3d_guard_colours<FAST>(lds, cx, marching, iv.w, prev_skipped, prev_rgb, ppx, ppy, ppz, skipped, rgb, px, py, pz);
             if (have) {
                 if (!first) p3d_composite_interval<false>(acc, st, iv, prev_rgb, rgb, ppx, ppy, ppz, px, py, pz);
                 st.prev_t = t; st.prev_sigma = sigma;
+                if constexpr (CARRY_POS) { ppx = px; ppy = py; ppz = pz; }  // o + prev_t * d of the next step, bit for bit: the same expression
                 prev_rgb = rgb;
                 prev_skipped = skipped;
                 first = false;

@@ -11,7 +11,9 @@ kernel's Morton lane order, and counts decode steps per wave the way the kernel 
   sample that decoded to the masked density).
 
 It also prints the final pass's lane occupancy (decodes / (steps x 32)) and what perfect packing of a wave's decodes would
-give, i.e. the ceiling of any scheme that regroups lanes.  Stride 4 on the surface scene at 48+48: 23.0 coarse + 48.5 final
+give, i.e. the ceiling of any scheme that regroups lanes; and the final wave-steps that carry at least one live unmasked lane
+(the steps whose colour part runs), the colour samples per wave and their lane occupancy: what a shortcut that needs all 32
+lanes of a step to agree can hope for.  Stride 4 on the surface scene at 48+48: 23.0 coarse + 48.5 final
 wave-steps of 144 = 0.497 (the kernel's own counter, decode_steps_executed_frac: 0.498), occupancy 0.85, packed 41.6.
 """
 import argparse
@@ -29,7 +31,8 @@ from oracle import oracle  # noqa: E402
 
 def tile_steps(scene="surface", stride=4, Sc=48, Sf=48, res=512, azim=20.0):
     """The view's tiles (tx, ty) with tx % stride == ty % stride == 0, each rendered as one wave: returns (ty, tx, coarse wave-steps,
-    final wave-steps, decodes of the final pass, fraction of the coarse samples cropped), arrays over those tiles in row-major order."""
+    final wave-steps, decodes of the final pass, fraction of the coarse samples cropped, per-tile colour statistics of the final pass:
+    colour_steps, colour_samples, coarse_again), arrays over those tiles in row-major order."""
     spec = importlib.util.spec_from_file_location("p3d_cameras", os.path.join(ROOT, "panic3d-anime-reconstruction_amd", "cameras.py"))
     cams = importlib.util.module_from_spec(spec)  # (the cameras alone: the package itself would load the HIP library)
     spec.loader.exec_module(cams)
@@ -70,7 +73,15 @@ def tile_steps(scene="surface", stride=4, Sc=48, Sf=48, res=512, azim=20.0):
     known = cropped(tm) | ((perm < Sc) & (sm <= -999))
     need = (transmittance_before(tm, sm) >= 1e-60) & ~known
     n_l = need.sum(axis=1).reshape(W, 32)
-    return np.array(tys), np.array(txs), steps_c, n_l.max(axis=1), n_l.sum(axis=1), float(cropped(tc).mean())
+    # the colour part of a final step runs if a lane that decodes in it finds its sample unmasked.  A lane's k-th needed sample is
+    # decoded in the wave's k-th final step: bring every ray's needed samples to the front, in merged order
+    order = np.argsort(~need, axis=1, kind="stable")
+    colour = np.take_along_axis(need & (sm > -999), order, axis=1)  # [ray, step]: the lane decodes an unmasked sample in this step
+    again = np.take_along_axis(need & (sm > -999) & (perm < Sc), order, axis=1)  # ... which the coarse pass had decoded already
+    colour_w = colour.reshape(W, 32, -1)
+    stats = dict(colour_steps=colour_w.any(axis=1).sum(axis=1), colour_samples=colour_w.sum(axis=(1, 2)),
+                 coarse_again=again.reshape(W, -1).sum(axis=1))
+    return np.array(tys), np.array(txs), steps_c, n_l.max(axis=1), n_l.sum(axis=1), float(cropped(tc).mean()), stats
 
 
 def main():
@@ -81,12 +92,17 @@ def main():
     ap.add_argument("--sf", type=int, default=48)
     a = ap.parse_args()
     Sc, Sf = a.sc, a.sf
-    _, _, steps_c, mx, tot, crop = tile_steps(a.scene, a.stride, Sc, Sf)
+    _, _, steps_c, mx, tot, crop, st = tile_steps(a.scene, a.stride, Sc, Sf)
     W, S = len(mx), Sc + Sf
     print(f"{a.scene} {Sc}+{Sf}, {W} waves ({W * 32} rays): coarse samples cropped {crop:.3f}")
     print(f"coarse wave-steps {steps_c.mean():.1f} of {Sc}; final wave-steps {mx.mean():.1f} of {S}; "
           f"total {(steps_c + mx).mean():.1f} of {Sc + S} = {(steps_c + mx).mean() / (Sc + S):.4f}")
     print(f"final pass: lane occupancy {tot.sum() / (mx.sum() * 32):.3f}; perfectly packed {np.ceil(tot / 32).mean():.1f} wave-steps")
+    # what a wave-uniform shortcut of the walk can hope for: the final steps in which NO lane holds a live, unmasked sample
+    cs, cn = st["colour_steps"], st["colour_samples"]
+    print(f"final wave-steps with at least one live unmasked lane (the colour part runs) {cs.mean():.1f} of {mx.mean():.1f}; "
+          f"colour samples per wave {cn.mean():.0f}, lane occupancy {cn.sum() / (cs.sum() * 32):.3f}; "
+          f"{st['coarse_again'].mean():.0f} of them coarse samples decoded a second time")
 
 
 if __name__ == "__main__":
