@@ -267,4 +267,35 @@ P3D_IMP_UNROLL
     for (int w = 0; w < 6; ++w)
         if (w < nmw) put(w, knw[w], slw[w]);
 }
+
+// ---- the draw rows of a ray (jitter [Sc], u [Sf]) as 16-byte loads, and the stratified depths shared out
+// A ray's row is contiguous and, where the launch says so (RenderParams::wide_rows, p3d_render_plan.hpp), every piece of four
+// floats a half takes is 16-byte aligned.  The first `pieces` (wave-uniform, <= MAXP) pieces of `row`, all in flight together:
+template <int MAXP>
+__device__ __forceinline__ void p3d_load_row_pieces(const float* row, int pieces, f32x4 (&out)[MAXP]) {
+P3D_IMP_UNROLL
+    for (int q = 0; q < MAXP; ++q)
+        if (q < pieces) out[q] = *(const f32x4*)(row + 4 * q);
+}
+// ... and N floats (whole pieces) of it into a register row
+template <int N>
+__device__ __forceinline__ void p3d_load_row_wide(const float* row, float (&out)[N]) {
+    static_assert(N % 4 == 0, "whole 16-byte pieces");
+P3D_IMP_UNROLL
+    for (int q = 0; q < N / 4; ++q) {
+        const f32x4 v = *(const f32x4*)(row + 4 * q);
+        out[4 * q] = v.x; out[4 * q + 1] = v.y; out[4 * q + 2] = v.z; out[4 * q + 3] = v.w;
+    }
+}
+// Half h has made the stratified depths [h * Sc/2, (h + 1) * Sc/2) in index order: first / last are the ends of its run, unsorted
+// says whether two neighbours INSIDE it are out of order, tcmin / tcmax are its extrema.  One exchange gives both halves the ray's:
+// the comparison across the cut, t[Sc/2] < t[Sc/2 - 1], joins the flag, and min / max are order-free, hence exact.
+__device__ __forceinline__ void p3d_stratified_combine(int h, float first, float last, bool& unsorted, float& tcmin, float& tcmax) {
+    const float other = __shfl_xor(h ? first : last, 32);  // half 0: t[Sc/2]; half 1: t[Sc/2 - 1]
+    const int uo = __shfl_xor((int)unsorted, 32);
+    const float mn = __shfl_xor(tcmin, 32), mx = __shfl_xor(tcmax, 32);
+    unsorted = unsorted || uo != 0 || (h ? first < other : other < last);
+    tcmin = __builtin_fminf(tcmin, mn);
+    tcmax = __builtin_fmaxf(tcmax, mx);
+}
 #endif

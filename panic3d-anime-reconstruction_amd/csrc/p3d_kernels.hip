@@ -303,6 +303,12 @@ __global__ __launch_bounds__(P3D_WG, 2) void k_decode_features(DecodeFeatParams 
 // tolerance-mode LDS image; the known-masked bits of the coarse samples live in three registers.  With jitter in [0, 1), as
 // torch.rand_like produces it, the stratified depths can be out of order only between NEIGHBOURS (rounding), which the sorted
 // accessor resolves with two more reads; any other disorder takes an exact O(Sc^2) selection (p3d_coarse_rank, p3d_importance.hpp).
+// The draw rows: a ray's jitter row (Sc floats) and u row (Sf) are contiguous, and where the launch says so (RenderParams::wide_rows,
+// p3d_render_wide_rows: tensors passed in, aligned, rows of whole pieces) they are read as 16-byte pieces under ONE wave-uniform
+// branch per row.  The jitter pieces are requested in front of the weight copy, so their round trip runs under it; half h makes
+// the stratified depths [h * Sc/2, (h + 1) * Sc/2) and one exchange joins the halves' flags and extrema (p3d_stratified_combine);
+// TCG reads the row one batch of eight ahead of the decodes that use it.  The same operations on the same operands: no result bit
+// changes.  Any other launch (in-kernel draws, an unaligned view, Sc % 8 != 0) runs the scalar loads, both halves all depths.
 // The final pass merges on the fly (ties: coarse first = stable), decodes and composites [rgb | xyz]: renderer.py:243-259.
 // Every lane walks ITS OWN merged list.  With the early-outs on, a lane first consumes — without a decode — every sample
 // whose sigma = -1000 is already known (cropped by position, or a coarse sample the coarse pass really decoded and found
@@ -325,17 +331,39 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     static_assert(!TCG || p3d_render_tcg(NF, DUMP, EARLY), "TCG exists only for the production 96-key kernel");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     P3D_PHASE_START();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+    const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
+    constexpr int JP = TCG ? 2 : P3D_WIDE_MAX_PIECES;  // 16-byte pieces of the jitter row a lane holds
+#if P3D_WIDE_ROWS
+    // ---- tile -> ray, wave set-up, and the jitter row requested: all of it in front of the weight copy, whose barrier every wave
+    // waits at with nothing else in flight.  Half h takes the pieces of ITS Sc/2 stratified depths (TCG: both halves the first batch
+    // of eight, the coarse loop needs every depth in both).  A wave without a tile sets up the last tile's rays, requests no row and
+    // leaves behind the barrier.
+    const long long tile = p3d_render_wave_tile(p, wave);
+    const bool has_tile = tile < p.ntiles;
+    const P3dRayCtx cx = p3d_ray_setup(p, p3d_render_tile_ray(p, has_tile ? tile : p.ntiles - 1, j), Sc, Sf);
+    const bool wide_j = has_tile && (p.wide_rows & P3D_WIDE_JITTER) != 0;  // wave-uniform
+    const bool wide_u = (p.wide_rows & P3D_WIDE_U) != 0;
+    f32x4 jw[JP];
+    if (wide_j) p3d_load_row_pieces<JP>(cx.jit + (TCG ? 0 : h * (Sc >> 1)), TCG ? 2 : (Sc >> 3), jw);
     p3d_load_mlp_to_lds(lds, p.w0, p.b0, p.w1, p.b1, !FAST);
     if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+    if (!has_tile) return;  // no workgroup barrier below this line
+    P3D_PHASE(P3D_PH_WEIGHTS);
+#else
+    p3d_load_mlp_to_lds(lds, p.w0, p.b0, p.w1, p.b1, !FAST);
+    if constexpr (FAST) p3d_load_mlp_f16_to_lds(lds, p.w0, p.w1);
+    __syncthreads();
     // ---- tile -> ray, wave set-up
     const long long tile = p3d_render_wave_tile(p, wave);
     if (tile >= p.ntiles) return;  // no workgroup barrier below this line
     P3D_PHASE(P3D_PH_WEIGHTS);
-    float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * 32;  // per-wave rows, 16-B aligned
-    const int Sc = p.Sc, Sf = P3D_NF_EXACT(NF) ? NF : p.Sf, S = Sc + Sf;
     const P3dRayCtx cx = p3d_ray_setup(p, p3d_render_tile_ray(p, tile, j), Sc, Sf);
+    constexpr bool wide_j = false, wide_u = false;
+    f32x4 jw[JP];
+#endif
+    float* wl = lds + (FAST ? P3D_LDS_FAST_FLOATS : P3D_LDS_MLP_FLOATS) + 4 + (size_t)wave * p.lds_rows * 32;  // per-wave rows, 16-B aligned
     const bool active = cx.active;
     const size_t ray = cx.ray;
     const float ox = cx.ox, oy = cx.oy, oz = cx.oz, dx = cx.dx, dy = cx.dy, dz = cx.dz;
@@ -367,6 +395,31 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     float tcmin = __builtin_inff(), tcmax = -__builtin_inff();  // extrema of the coarse depths
     if constexpr (!TCG) {
         float prev = -__builtin_inff();
+        if (wide_j) {
+            // the pieces requested in front of the weight copy: half h makes the depths [h * Sc/2, (h + 1) * Sc/2) and writes their
+            // rows (and dump entries); one exchange then gives both halves the ray's flag and extrema (p3d_importance.hpp)
+            const int c0 = h * (Sc >> 1);
+            float first = 0.0f;
+#pragma unroll
+            for (int q = 0; q < JP; ++q) {
+                if (8 * q < Sc) {  // wave-uniform
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int i = c0 + 4 * q + e;
+                        const float t = p3d_stratified_depth(i, Sc, jw[q][e], sp);
+                        tcA[i * 32 + j] = t;
+                        unsorted |= (t < prev);
+                        prev = t;
+                        if (q == 0 && e == 0) first = t;
+                        tcmin = __builtin_fminf(tcmin, t);
+                        tcmax = __builtin_fmaxf(tcmax, t);
+                        if constexpr (DUMP) if (active && p.dumps.depths_coarse) p.dumps.depths_coarse[ray * Sc + i] = t;
+                    }
+                }
+            }
+            p3d_stratified_combine(h, first, prev, unsorted, tcmin, tcmax);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the coarse loop reads the rows the other half wrote
+        } else
         for (int i0 = 0; i0 < Sc; i0 += 8) {  // eight loads of the jitter row in flight (one at a time exposed a global-load latency per sample)
             float jv[8];
 #pragma unroll
@@ -397,8 +450,16 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             float prev = -__builtin_inff(), pmax = -__builtin_inff();  // previous depth; maximum of all depths before it
             for (int i0 = 0; i0 < Sc; i0 += 8) {
                 float jv[8];
+                if (wide_j) {
+                    // the batch is here (the first one requested in front of the weight copy); the next batch's two pieces are
+                    // requested in front of this batch's eight decodes
 #pragma unroll
-                for (int q = 0; q < 8; ++q) jv[q] = cx.jitter(i0 + q < Sc ? i0 + q : Sc - 1);
+                    for (int q = 0; q < 8; ++q) jv[q] = jw[q >> 2][q & 3];
+                    if (i0 + 8 < Sc) p3d_load_row_pieces<JP>(cx.jit + i0 + 8, 2, jw);  // wave-uniform
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) jv[q] = cx.jitter(i0 + q < Sc ? i0 + q : Sc - 1);
+                }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int i = i0 + q;
@@ -477,8 +538,12 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             static_assert(H % DB == 0, "whole batches of draws per half");
             const int d0 = h * H;
             float tf[H];
+            if (wide_u) {  // wave-uniform: the half row as H / 4 16-byte loads
+                p3d_load_row_wide<H>(cx.uu + d0, tf);
+            } else {
 #pragma unroll
-            for (int i = 0; i < H; ++i) tf[i] = cx.u(d0 + i);  // every load of the half row issued before the first search
+                for (int i = 0; i < H; ++i) tf[i] = cx.u(d0 + i);  // every load of the half row issued before the first search
+            }
 #pragma unroll
             for (int i0 = 0; i0 < H; i0 += DB) {
                 float ub[DB], vb[DB];
@@ -517,8 +582,17 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             // (the same text as k_render_slots' below, on purpose: behind one shared helper every LDS read of the searches got one
             // more VALU operation in front of it, +260-370 instructions per kernel, profiles/r08_resource_*.txt)
             float tf[NF];
+            if (wide_u) {  // wave-uniform: Sf is whole pieces
 #pragma unroll
-            for (int i = 0; i < NF; ++i) tf[i] = (i < Sf) ? cx.u(i) : 0.0f;  // every load of the row issued before the first search
+                for (int q = 0; q < NF / 4; ++q) {
+                    f32x4 v = 0.0f;
+                    if (4 * q < Sf) v = *(const f32x4*)(cx.uu + 4 * q);
+                    tf[4 * q] = v.x; tf[4 * q + 1] = v.y; tf[4 * q + 2] = v.z; tf[4 * q + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NF; ++i) tf[i] = (i < Sf) ? cx.u(i) : 0.0f;  // every load of the row issued before the first search
+            }
 #pragma unroll
             for (int i0 = 0; i0 < NF; i0 += DB) {
                 if (i0 < Sf) {  // wave-uniform
@@ -552,8 +626,13 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             for (int i0 = 0; i0 < Sf; i0 += DB) {
                 float ub[DB], vb[DB];
                 int kb[DB];
+                if (wide_u) {  // wave-uniform: Sf is whole batches
+                    static_assert(DB == 8, "a batch of draws is two pieces");
+                    p3d_load_row_wide<DB>(cx.uu + i0, ub);
+                } else {
 #pragma unroll
-                for (int q = 0; q < DB; ++q) ub[q] = cx.u(i0 + q < Sf ? i0 + q : Sf - 1);
+                    for (int q = 0; q < DB; ++q) ub[q] = cx.u(i0 + q < Sf ? i0 + q : Sf - 1);
+                }
                 p3d_inverse_cdf<DB, 32>(wcA, tc_of, Ns, j, ub, vb, kb);
 #pragma unroll
                 for (int q = 0; q < DB; ++q) {
@@ -1504,6 +1583,7 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     RenderParams p;
     p.planes = planes; p.rays_o = rays_o; p.rays_d = rays_d; p.jitter = jitter; p.u = u;
     p.rng = rng; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
+    p.wide_rows = p3d_render_wide_rows(rng, jitter, u, Sc, Sf);
     p.w0 = w0; p.b0 = b0; p.w1 = w1; p.b1 = b1;
     p.out_feat = out_feat; p.out_depth = out_depth; p.out_wsum = out_wsum; p.out_xyz = out_xyz;
     p.gminmax = (uint32_t*)workspace;

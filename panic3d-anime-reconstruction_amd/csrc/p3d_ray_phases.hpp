@@ -34,6 +34,7 @@ struct RenderParams {
     int lds_rows;     // rows (of 32 floats) of per-wave LDS
     int rng;          // p3d_render_rng_f32: the two draws come from the counter-based generator of include/p3d_numerics.h
     uint32_t seed_lo, seed_hi;
+    int wide_rows;    // k_render: P3D_WIDE_JITTER | P3D_WIDE_U, the rows it may load as 16-byte pieces (p3d_render_wide_rows)
     P3dTileOrder order;  // k_render: the XCD tile order (p3d_render_plan.hpp)
     P3dDecodeCfg cfg;
 };

@@ -6,6 +6,7 @@
 //   p3d_tile_of_block / p3d_tile_screen   k_render's tile order itself, compiled for the host AND the device (the kernel calls them)
 //   p3d_render_plan              the plan of one launch: a pure function of its shape and options
 //   p3d_render_plan_workspace_bytes   what p3d_render_workspace_bytes answers
+//   p3d_render_wide_rows         which of the launch's two draw rows k_render may load as 16-byte pieces (needs the pointers)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -155,6 +156,33 @@ struct RenderPlan {
     P3dTileOrder order;   // ... and the order the launch runs in: that one, or the balanced pieces where the shape divides into them
     long long decode_steps_full;  // wave-level decode steps with every sample decoded
 };
+
+// ---- wide draw rows (k_render; k_render_slots keeps its scalar loads)
+// A ray's jitter row is Sc contiguous floats and its u row Sf; each lane half of k_render takes half of a row.  Where every such
+// share is whole 16-byte pieces the kernel loads it as pieces, the jitter row in front of the weight copy (p3d_kernels.hip).  The
+// launch decides per row, once, and hands the kernel the bits (RenderParams::wide_rows, wave-uniform):
+//   no in-kernel draws; the row's base pointer 16-byte aligned; the row's length a multiple of 8 floats (so that the row of every
+//   ray, and the second half's share of it, start on a piece); the jitter row also at most 2 * 4 * P3D_WIDE_MAX_PIECES floats, what
+//   the kernel holds in registers across the weight copy.
+// Otherwise the kernels run the scalar loads.  -DP3D_WIDE_ROWS=0 rebuilds the kernels without the pieces (the A/B of DESIGN.md section 6).
+#ifndef P3D_WIDE_ROWS
+#define P3D_WIDE_ROWS 1
+#endif
+#define P3D_WIDE_JITTER 1
+#define P3D_WIDE_U 2
+#define P3D_WIDE_MAX_PIECES 12  // per half: Sc <= 96
+static inline int p3d_render_wide_rows(int rng, const void* jitter, const void* u, int Sc, int Sf) {
+#if P3D_WIDE_ROWS
+    if (rng) return 0;
+    int bits = 0;
+    if (jitter && ((uintptr_t)jitter & 15u) == 0 && Sc % 8 == 0 && Sc / 8 <= P3D_WIDE_MAX_PIECES) bits |= P3D_WIDE_JITTER;
+    if (u && ((uintptr_t)u & 15u) == 0 && Sf > 0 && Sf % 8 == 0) bits |= P3D_WIDE_U;
+    return bits;
+#else
+    (void)rng; (void)jitter; (void)u; (void)Sc; (void)Sf;
+    return 0;
+#endif
+}
 
 static inline size_t p3d_render_plan_workspace_bytes(int N) {
     return 256 + (size_t)(N > 0 ? N : 0) * 8;  // global min / max + decode-step count, then one min / max pair per view
