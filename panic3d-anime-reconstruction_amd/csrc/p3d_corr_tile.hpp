@@ -46,6 +46,15 @@ __device__ __forceinline__ float sg_block_sum(float v, float* red) {
     return red[0];
 }
 
+// The bias_act backward's rule for one value, defined once: y is the layer's output before any residual, gy its cotangent.  Used by
+// k_sg_bias_act_bwd / k_sg_noise_bwd (p3d_synthesis_grad.hip) and in the store of k_conv2d_mask (p3d_r1.hip).
+__device__ __forceinline__ float sg_gz(float y, float gy, int act, float alpha, float gain, float clamp) {
+    if (clamp >= 0.f && !(fabsf(y) < clamp)) return 0.f;
+    float g = gy * gain;
+    if (act == 1 && !(y > 0.f)) g = g * alpha;
+    return g;
+}
+
 // x [N][Ci][Hi][Wi], wk [taps][Ci][Co] -> [N][Co][Ho][Wo]; blockIdx = (pixel tile, channel tile, sample)
 struct SgCorr {
     const float* x;

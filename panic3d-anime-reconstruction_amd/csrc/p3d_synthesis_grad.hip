@@ -21,14 +21,7 @@
 
 static inline size_t sg_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// ---- bias_act backward ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sg_gz(float y, float gy, int act, float alpha, float gain, float clamp) {
-    if (clamp >= 0.f && !(fabsf(y) < clamp)) return 0.f;
-    float g = gy * gain;
-    if (act == 1 && !(y > 0.f)) g = g * alpha;
-    return g;
-}
-
+// ---- bias_act backward (the rule itself, sg_gz, is in p3d_corr_tile.hpp: the R1 tangent layer of p3d_r1.hip applies it in its store) ----
 __global__ __launch_bounds__(SG_WG) void k_sg_bias_act_bwd(const float* __restrict__ y, const float* g_y, int C, int64_t HW, int act,
                                                            float alpha, float gain, float clamp, const float* __restrict__ dscale,
                                                            float* g_out, float* __restrict__ g_bias_nc) {

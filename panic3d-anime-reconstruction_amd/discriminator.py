@@ -6,7 +6,9 @@ strict=True)` works in both directions and `c.D_kwargs.class_name` can name this
 Every convolution layer is ONE launch of ops.conv2d_act after its FIR (bias, lrelu, gain, clamp and the resnet block's residual add
 in the convolution's store); the minibatch standard deviation is ops.minibatch_std; the two fully-connected layers of the epilogue
 and the conditioning's mapping network are stylegan2.FullyConnectedLayer / MappingNetwork.  Under autograd each layer records a
-first-order HIP backward; a double backward — the R1 penalty — raises.
+first-order HIP backward; a double backward — the R1 penalty — raises, unless DualDiscriminator.set_r1_grad() has
+switched on the recorded backward: then a backward under create_graph=True is differentiable once more, which is
+what the loss's Dreg / Dboth phases need, and everything else — the forward, a plain backward — is unchanged.
 
 Precision: `num_fp16_res`, `use_fp16` and `fp16_channels_last` are accepted and the network runs in binary32, as the reference does
 on CPU and under force_fp32; `conv_clamp` is applied exactly as the reference applies it in fp32.
@@ -43,6 +45,7 @@ class Conv2dLayer(_CacheFree):
                 self.register_buffer("bias", bias)
             else:
                 self.bias = None
+        self.r1_grad = False  # DualDiscriminator.set_r1_grad
 
     def _wk(self):
         """`weight * weight_gain` (networks_stylegan2.py:181) as the kernel's [taps][Ci][Co] operand.  No-grad: made once per parameter
@@ -73,14 +76,15 @@ class Conv2dLayer(_CacheFree):
             f = self.resample_filter
             p = self.padding + (f.shape[-1] - self.down + 1) // 2, self.padding + (f.shape[-1] - self.down) // 2
             if k == 1:
-                x = ops.fir(x, f, down=2, padding=[p[0], p[1], p[0], p[1]])
+                x = ops.fir(x, f, down=2, padding=[p[0], p[1], p[0], p[1]], r1=self.r1_grad)
             else:
-                x = ops.fir(x, f, padding=[p[0], p[1], p[0], p[1]])
+                x = ops.fir(x, f, padding=[p[0], p[1], p[0], p[1]], r1=self.r1_grad)
                 stride = 2
             pad = 0
         act_gain = self.act_gain * gain
         act_clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
-        return ops.conv2d_act(x, self._wk(), self.bias, act=self.activation, gain=act_gain, clamp=act_clamp, stride=stride, pad=pad, res=res)
+        return ops.conv2d_act(x, self._wk(), self.bias, act=self.activation, gain=act_gain, clamp=act_clamp, stride=stride, pad=pad, res=res,
+                              r1=self.r1_grad)
 
     def extra_repr(self):
         return f"in_channels={self.in_channels:d}, out_channels={self.out_channels:d}, activation={self.activation:s}, up={self.up}, down={self.down}"
@@ -139,9 +143,10 @@ class MinibatchStdLayer(torch.nn.Module):
     def __init__(self, group_size, num_channels=1):
         super().__init__()
         self.group_size, self.num_channels = group_size, num_channels
+        self.r1_grad = False  # DualDiscriminator.set_r1_grad
 
     def forward(self, x):
-        return ops.minibatch_std(x, self.group_size, self.num_channels)
+        return ops.minibatch_std(x, self.group_size, self.num_channels, r1=self.r1_grad)
 
     def extra_repr(self):
         return f"group_size={self.group_size}, num_channels={self.num_channels:d}"
@@ -180,17 +185,18 @@ class DiscriminatorEpilogue(torch.nn.Module):
         return f"resolution={self.resolution:d}, architecture={self.architecture:s}"
 
 
-def filtered_resizing(image_orig_tensor, size, f, filter_mode="antialiased"):
-    """dual_discriminator.py:86-102.  The interpolations are torch's (plumbing); the 'classic' mode's two FIR passes are ops.fir."""
+def filtered_resizing(image_orig_tensor, size, f, filter_mode="antialiased", r1=False):
+    """dual_discriminator.py:86-102.  The interpolations are torch's (plumbing); the 'classic' mode's two FIR passes are ops.fir (r1:
+    differentiable to any order, DualDiscriminator.set_r1_grad)."""
     interp = torch.nn.functional.interpolate
     if filter_mode == "antialiased":
         return interp(image_orig_tensor, size=(size, size), mode="bilinear", align_corners=False, antialias=True)
     if filter_mode == "classic":
         fw = f.shape[-1]  # upsample2d (upfirdn2d.py:341-350): padding ((fw + 1) // 2, (fw - 2) // 2), gain 4
-        y = ops.fir(image_orig_tensor, f, up=2, padding=[(fw + 1) // 2, (fw - 2) // 2] * 2, gain=4)
+        y = ops.fir(image_orig_tensor, f, up=2, padding=[(fw + 1) // 2, (fw - 2) // 2] * 2, gain=4, r1=r1)
         y = interp(y, size=(size * 2 + 2, size * 2 + 2), mode="bilinear", align_corners=False)
         p = [-1 + (fw - 2 + 1) // 2, -1 + (fw - 2) // 2] * 2  # downsample2d (upfirdn2d.py:378-387) with padding -1
-        return ops.fir(y.contiguous(), f, down=2, padding=p, flip_filter=True)
+        return ops.fir(y.contiguous(), f, down=2, padding=p, flip_filter=True, r1=r1)
     if filter_mode == "none":
         return interp(image_orig_tensor, size=(size, size), mode="bilinear", align_corners=False)
     if type(filter_mode) == float:
@@ -229,9 +235,24 @@ class DualDiscriminator(torch.nn.Module):
         self.b4 = DiscriminatorEpilogue(channels_dict[4], cmap_dim=cmap_dim, resolution=4, **epilogue_kwargs, **common_kwargs)
         self.register_buffer("resample_filter", ops.setup_filter([1, 3, 3, 1]))
         self.disc_c_noise = disc_c_noise
+        self.r1_grad = False
+
+    def set_r1_grad(self, state=True):
+        """Opt-in: let a backward that autograd records (torch.autograd.grad(..., create_graph=True), the R1 penalty of the loss's Dreg /
+        Dboth phases) be differentiated once more.  With the switch on, every convolution layer, the minibatch standard
+        deviation, the FIR passes and the epilogue's activated fully-connected layer record their first backward through Functions
+        whose own backward is HIP (include/p3d_r1.h); the gradients of that first backward are the plain backward's bits.  The forward
+        and a plain backward are today's in either state.  Off (the default): such a backward raises ops.R1_MESSAGE."""
+        state = bool(state)
+        self.r1_grad = state
+        for m in self.modules():
+            if isinstance(m, (Conv2dLayer, MinibatchStdLayer)):
+                m.r1_grad = state
+        self.b4.fc.r1_grad = state
+        return state
 
     def forward(self, img, c, cond, update_emas=False, **block_kwargs):
-        image_raw = filtered_resizing(img["image_raw"], size=img["image"].shape[-1], f=self.resample_filter)
+        image_raw = filtered_resizing(img["image_raw"], size=img["image"].shape[-1], f=self.resample_filter, r1=self.r1_grad)
         img = torch.cat([img["image"], image_raw], 1)
         _ = update_emas  # unused (dual_discriminator.py:162)
         x = None

@@ -7,7 +7,8 @@ alpha and depth terms and their gradients in one launch).  G, D, the resizes of 
 the caller's modules and torch plumbing.  Random draws come from torch's global generator, on the same device and in the same order
 as the reference's, so a seeded CPU run of both sees the same numbers.
 
-Not covered: the R1 penalty (see StyleGAN2LossOrthoCondA), the augmentation pipeline (any callable is applied as the reference
+The R1 penalty (Dreg / Dboth) runs when the discriminator has its recorded backward switched on (D.set_r1_grad(), DESIGN.md §4.21;
+see StyleGAN2LossOrthoCondA); the sum of squares is ops.r1_penalty.  Not covered: the augmentation pipeline (any callable is applied as the reference
 applies its own; its image-side operator is ops.augment_apply, DESIGN.md §4.20, but the pipe module that draws the parameters is not
 ported).  LPIPS is any callable returning [N]; panic3d_amd.lpips.LPIPSLoss() is the HIP one
 (DESIGN.md §4.14).
@@ -67,9 +68,12 @@ class StyleGAN2LossOrthoCondA:
     Phases: Gcond, Gside-left / -right / -back, Grand, Gmain (with the lossmask_mode_adv / lossmask_mode_recon branches), Greg
     (reg_type l1, monotonic-detach, monotonic-fixed), Dmain, and Gboth / Dboth as the reference combines them.
 
-    R1: with r1_gamma > 0 a Dreg or Dboth phase raises RuntimeError(ops.R1_MESSAGE) before any forward.  The penalty differentiates
-    the discriminator's input gradient a second time, and the discriminator's HIP backward is first order only; running the forward
-    first would spend a generator and a discriminator pass on a phase that cannot finish.
+    R1: the penalty differentiates the discriminator's input gradient a second time.  The discriminator's HIP backward is first order
+    unless its recorded backward is switched on: with D.r1_grad true (DualDiscriminator.set_r1_grad()), Dreg and Dboth run as the
+    reference's (:690-738: the real images' logits, torch.autograd.grad(..., create_graph=True, only_inputs=True) inside
+    ops.no_weight_gradients(), ops.r1_penalty, the backward of the penalty times r1_gamma / 2).  Without the switch, with r1_gamma > 0
+    a Dreg or Dboth phase raises RuntimeError(ops.R1_MESSAGE) before any forward; running the forward first would spend a generator
+    and a discriminator pass on a phase that cannot finish.
 
     A defect of the reference that is not reproduced: its Greg style-mixing lines (:591, :635, :679) name the undefined variables z
     and c, a NameError whenever style_mixing_prob > 0; gen_z and gen_c are used here.
@@ -197,7 +201,7 @@ class StyleGAN2LossOrthoCondA:
             phase = {"Greg": "none", "Gboth": "Gmain"}.get(phase, phase)
         if self.r1_gamma == 0:
             phase = {"Dreg": "none", "Dboth": "Dmain"}.get(phase, phase)
-        if phase in ("Dreg", "Dboth"):
+        if phase in ("Dreg", "Dboth") and not getattr(self.D, "r1_grad", False):
             raise RuntimeError(ops.R1_MESSAGE)
         blur_sigma = max(1 - cur_nimg / (self.blur_fade_kimg * 1e3), 0) * self.blur_init_sigma if self.blur_fade_kimg > 0 else 0
         fade = min(cur_nimg / (self.gpc_reg_fade_kimg * 1e3), 1) if self.gpc_reg_fade_kimg > 0 else 1
@@ -294,17 +298,33 @@ class StyleGAN2LossOrthoCondA:
             (F.l1_loss(a, b) * rk["density_reg"]).mul(gain).backward()
 
         # Dmain: minimise the logits of generated images, maximise those of real ones
-        if phase == "Dmain":
+        loss_Dgen = 0
+        if phase in ("Dmain", "Dboth"):
             gen_img, _ = self.run_G(gen_z, gen_c, real_cond, swapping_prob=swapping_prob, neural_rendering_resolution=res, update_emas=True)
             gen_logits = self.run_D(gen_img, gen_c, real_cond, blur_sigma=blur_sigma, update_emas=True)
             report("Loss/scores/fake", gen_logits)
             report("Loss/signs/fake", gen_logits.sign())
             loss_Dgen = F.softplus(gen_logits)
             loss_Dgen.mean().mul(gain).backward()
-            real = {"image": real_img["image"].detach().requires_grad_(False), "image_raw": real_img["image_raw"].detach().requires_grad_(False)}
-            real_logits = self.run_D(real, real_c, real_cond, blur_sigma=blur_sigma)
+
+        # Dmain: ... and maximise those of real ones; Dreg: the R1 penalty on the real images (:702-738)
+        if phase in ("Dmain", "Dreg", "Dboth"):
+            with_r1 = phase in ("Dreg", "Dboth")
+            real = {"image": real_img["image"].detach().requires_grad_(with_r1), "image_raw": real_img["image_raw"].detach().requires_grad_(with_r1)}
+            real_logits = self.run_D(real, real_c, real_cond, blur_sigma=blur_sigma)  # (run_D replaces real["image"] by its blurred version)
             report("Loss/scores/real", real_logits)
             report("Loss/signs/real", real_logits.sign())
-            loss_Dreal = F.softplus(-real_logits)
-            report("Loss/D/loss", loss_Dgen + loss_Dreal)
-            loss_Dreal.mean().mul(gain).backward()
+            loss_Dreal = 0
+            if phase in ("Dmain", "Dboth"):
+                loss_Dreal = F.softplus(-real_logits)
+                report("Loss/D/loss", loss_Dgen + loss_Dreal)
+            loss_Dr1 = 0
+            if with_r1:
+                inputs = [real["image"], real["image_raw"]] if self.dual_discrimination else [real["image"]]
+                with ops.no_weight_gradients():
+                    r1_grads = torch.autograd.grad(outputs=[real_logits.sum()], inputs=inputs, create_graph=True, only_inputs=True)
+                r1_penalty = ops.r1_penalty(*r1_grads)
+                loss_Dr1 = r1_penalty * (self.r1_gamma / 2)
+                report("Loss/r1_penalty", r1_penalty)
+                report("Loss/D/reg", loss_Dr1)
+            (loss_Dreal + loss_Dr1).mean().mul(gain).backward()

@@ -1277,14 +1277,15 @@ def conv_wgrad(g, gmap, x, s, xmap, taps, domain, wk=None, dscale=None):
     return dw, gd
 
 
-def _upfirdn2d_adjoint(g, f, up, down, padding, flip_filter, gain, in_hw):
-    """The adjoint of upfirdn2d(x [.., in_hw], f, up, down, padding, flip_filter, gain) applied to g (upfirdn2d.py:236-245)."""
+def _upfirdn2d_adjoint(g, f, up, down, padding, flip_filter, gain, in_hw, op=None):
+    """The adjoint of upfirdn2d(x [.., in_hw], f, up, down, padding, flip_filter, gain) applied to g (upfirdn2d.py:236-245); op: the
+    operator to call in upfirdn2d's place (ops.fir when the call is to be recorded)."""
     px0, px1, py0, py1 = _parse_padding(padding)
     fh, fw = f.shape
     ih, iw = in_hw
     oh, ow = g.shape[-2:]
     p = [fw - px0 - 1, iw * up - ow * down + px0 - up + 1, fh - py0 - 1, ih * up - oh * down + py0 - up + 1]
-    return upfirdn2d(g.contiguous(), f, up=down, down=up, padding=p, flip_filter=not flip_filter, gain=gain)
+    return (op or upfirdn2d)(g.contiguous(), f, up=down, down=up, padding=p, flip_filter=not flip_filter, gain=gain)
 
 
 class _Upsample2dFn(torch.autograd.Function):
@@ -1474,12 +1475,14 @@ def _conv2d_act_impl(x, wk, bias, act, gain, clamp, stride, pad, res, want_pre=F
     return (out, pre) if want_pre else out
 
 
-def conv2d_act(x, wk, bias=None, act="linear", gain=None, clamp=None, stride=1, pad=0, res=None):
+def conv2d_act(x, wk, bias=None, act="linear", gain=None, clamp=None, stride=1, pad=0, res=None, r1=False):
     """Conv2dLayer's forward after any resampling, in one launch: clamp(act(corr(x, wk) + bias) * gain) (+ res).  x [N,Ci,H,W];
     wk [taps,Ci,Co] = the layer's weight * weight_gain as weight.permute(2, 3, 1, 0); gain None = the activation's default.
-    A plain call under no_grad; records the HIP backward (first order only) when an input requires grad — same forward bits."""
+    A plain call under no_grad; records the HIP backward when an input requires grad — same forward bits.  That backward is first order
+    only unless r1 is set (DualDiscriminator.set_r1_grad): then a backward that autograd records (create_graph=True) is itself
+    differentiable once more (the R1 penalty), and a plain backward is unchanged."""
     if _wants_grad(x, wk, bias, res):
-        return _Conv2dActFn.apply(x, wk, bias, res, (act, gain, clamp, int(stride), int(pad)))
+        return _Conv2dActFn.apply(x, wk, bias, res, (act, gain, clamp, int(stride), int(pad)), bool(r1))
     return _conv2d_act_impl(x, wk, bias, act, gain, clamp, int(stride), int(pad), res)
 
 
@@ -1499,6 +1502,42 @@ def _first_order(backward):
     return wrapper
 
 
+R1_THIRD_ORDER_MESSAGE = ("the discriminator's recorded HIP backward (set_r1_grad) is second order only: the backward of the R1 penalty "
+                          "cannot itself be recorded (create_graph=True); a third differentiation is not implemented")
+_NO_WEIGHT_GRADIENTS = [False]
+
+
+def _second_order(backward):
+    """_first_order for the Functions of the recorded backward, which are themselves first order: a third differentiation raises."""
+    inner = torch.autograd.function.once_differentiable(backward)
+
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled():
+            raise RuntimeError(R1_THIRD_ORDER_MESSAGE)
+        return inner(ctx, *grads)
+    return wrapper
+
+
+class no_weight_gradients:
+    """The reference's conv2d_gradfix.no_weight_gradients(): inside it, a recorded backward (r1) of the discriminator's convolution
+    layers computes input gradients only.  ctx.needs_input_grad is fixed when the forward runs, so torch.autograd.grad(...,
+    only_inputs=True) alone would still have every layer compute a weight and a bias gradient that nobody reads."""
+
+    def __enter__(self):
+        self.old, _NO_WEIGHT_GRADIENTS[0] = _NO_WEIGHT_GRADIENTS[0], True
+        return self
+
+    def __exit__(self, *exc):
+        _NO_WEIGHT_GRADIENTS[0] = self.old
+
+
+def _bias_act_backward_meta(pre, gy, meta):
+    act, gain, clamp = meta[:3]
+    idx, alpha, dg = _ACTS[act]
+    gz, gb, _ = bias_act_backward(pre, gy, idx, alpha, float(gain if gain is not None else dg), clamp)
+    return gz, gb
+
+
 _ONE_TAP = {}
 
 
@@ -1509,67 +1548,105 @@ def _one_tap(device):
     return f
 
 
+def _conv_input_grad(gz, wk, in_shape, stride, pad):
+    """The data gradient of one convolution layer from g_z (the cotangent after bias_act's backward): p3d_conv_dgrad_f32 with the
+    flipped, transposed weights, a stride-2 layer's g_z zero-interleaved first."""
+    _, Ci, Hi, Wi = in_shape
+    k = 3 if wk.shape[0] == 9 else 1
+    if k - 1 - pad < 0:
+        raise NotImplementedError("conv2d_act backward: pad > kernel_size - 1")
+    # gx[y] = sum_t gz[(y + pad - t) / stride] w[t] = sum_t' Z[y + t' - (k - 1 - pad)] w[k - 1 - t'], Z = gz with stride - 1 zeros
+    # between its values (positions past Z's end read 0, as Z's own continuation would)
+    Z = gz if stride == 1 else upfirdn2d(gz, _one_tap(gz.device), up=stride)
+    return conv_dgrad(Z, wk.detach().flip(0).transpose(1, 2).contiguous(), Ci, Hi, Wi, 1, k - 1 - pad)
+
+
+def _conv_weight_grad(gz, x, taps, stride, pad):
+    """The gradient of wk [taps,Ci,Co] of one convolution layer from g_z and the layer's input (or, in the R1 pass, the cotangent of
+    the input's gradient, which takes the input's place): p3d_conv_wgrad_f32 over the output's pixels."""
+    dw, _ = conv_wgrad(gz, (1, 0, 0), x.contiguous(), None, (stride, 1 if taps == 9 else 0, pad), taps, tuple(gz.shape[-2:]))  # [taps,Co,Ci]
+    return dw.transpose(1, 2).contiguous()
+
+
 class _Conv2dActFn(torch.autograd.Function):
     """Backward of one discriminator convolution layer: bias_act from the output before the residual, the data
     gradient on p3d_conv_dgrad_f32 (flipped, transposed weights; a stride-2 layer's cotangent zero-interleaved first: the adjoint
-    of a stride-2 correlation is a stride-1 correlation over it), the weight gradient split over the output's pixels."""
+    of a stride-2 correlation is a stride-1 correlation over it), the weight gradient split over the output's pixels.  With r1 set, a
+    backward that autograd records goes through _R1ConvFn: the same launches, differentiable once more."""
 
     @staticmethod
-    def forward(ctx, x, wk, bias, res, meta):
+    def forward(ctx, x, wk, bias, res, meta, r1=False):
         act, gain, clamp, stride, pad = meta
         if res is not None:
             y, pre = _conv2d_act_impl(x, wk, bias, act, gain, clamp, stride, pad, res, want_pre=True)
         else:
             y = pre = _conv2d_act_impl(x, wk, bias, act, gain, clamp, stride, pad, None)
-        ctx.meta = meta
-        ctx.save_for_backward(x, wk, pre)
+        ctx.meta, ctx.r1 = meta, r1
+        ctx.save_for_backward(x, wk, pre, *([bias] if r1 and bias is not None else []))
         return y
 
     @staticmethod
-    @_first_order
     def backward(ctx, gy):
-        x, wk, pre = ctx.saved_tensors
-        act, gain, clamp, stride, pad = ctx.meta
-        idx, alpha, dg = _ACTS[act]
+        if ctx.r1 and torch.is_grad_enabled():
+            return _Conv2dActFn._recorded(ctx, gy)
+        return _Conv2dActFn._plain(ctx, gy)
+
+    @staticmethod
+    def _recorded(ctx, gy):
+        x, wk, pre = ctx.saved_tensors[:3]
+        bias = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        _, _, _, stride, pad = ctx.meta
+        pre, gy = pre.detach(), gy.contiguous()
+        need = ctx.needs_input_grad
+        gx = _R1ConvFn.apply(gy, wk, bias, pre, ctx.meta, tuple(x.shape)) if need[0] else None
+        gwk = g_bias = None
+        if (need[1] or need[2]) and not _NO_WEIGHT_GRADIENTS[0]:
+            # the parameters' own first-order gradients, asked for in a recorded pass: today's values, as constants of the graph
+            with torch.no_grad():
+                gz, gb = _bias_act_backward_meta(pre, gy.detach(), ctx.meta)
+                gwk = _conv_weight_grad(gz, x.detach(), wk.shape[0], stride, pad) if need[1] else None
+                g_bias = gb.sum(0) if need[2] else None
+        return gx, gwk, g_bias, (gy if need[3] else None), None, None
+
+    @staticmethod
+    @_first_order
+    def _plain(ctx, gy):
+        x, wk, pre = ctx.saved_tensors[:3]
+        _, _, _, stride, pad = ctx.meta
         gy = gy.contiguous()
-        gz, gb, _ = bias_act_backward(pre, gy, idx, alpha, float(gain if gain is not None else dg), clamp)
-        N, Ci, Hi, Wi = x.shape
-        taps, _, Co = wk.shape
-        k = 3 if taps == 9 else 1
-        Ho, Wo = gz.shape[-2:]
-        gx = gwk = None
-        if ctx.needs_input_grad[0]:
-            if k - 1 - pad < 0:
-                raise NotImplementedError("conv2d_act backward: pad > kernel_size - 1")
-            # gx[y] = sum_t gz[(y + pad - t) / stride] w[t] = sum_t' Z[y + t' - (k - 1 - pad)] w[k - 1 - t'], Z = gz with stride - 1 zeros
-            # between its values (positions past Z's end read 0, as Z's own continuation would)
-            Z = gz if stride == 1 else upfirdn2d(gz, _one_tap(gz.device), up=stride)
-            gx = conv_dgrad(Z, wk.detach().flip(0).transpose(1, 2).contiguous(), Ci, Hi, Wi, 1, k - 1 - pad)
-        if ctx.needs_input_grad[1]:
-            dw, _ = conv_wgrad(gz, (1, 0, 0), x.contiguous(), None, (stride, 1 if k == 3 else 0, pad), taps, (Ho, Wo))  # [taps,Co,Ci]
-            gwk = dw.transpose(1, 2).contiguous()
+        gz, gb = _bias_act_backward_meta(pre, gy, ctx.meta)
+        gx = _conv_input_grad(gz, wk, x.shape, stride, pad) if ctx.needs_input_grad[0] else None
+        gwk = _conv_weight_grad(gz, x, wk.shape[0], stride, pad) if ctx.needs_input_grad[1] else None
         g_bias = gb.sum(0) if ctx.needs_input_grad[2] else None
-        return gx, gwk, g_bias, (gy if ctx.needs_input_grad[3] else None), None
+        return gx, gwk, g_bias, (gy if ctx.needs_input_grad[3] else None), None, None
 
 
 class _UpfirdnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, meta):
-        ctx.meta, ctx.hw = meta, tuple(x.shape[-2:])
+    def forward(ctx, x, meta, r1=False):
+        ctx.meta, ctx.hw, ctx.r1 = meta, tuple(x.shape[-2:]), r1
         return upfirdn2d(x, *meta)
 
     @staticmethod
-    @_first_order
     def backward(ctx, gy):
+        if ctx.r1 and torch.is_grad_enabled():
+            # linear: the adjoint, called through fir again, is recorded in turn and its own backward is the operator itself (as _BlurFn)
+            f, up, down, padding, flip_filter, gain = ctx.meta
+            return _upfirdn2d_adjoint(gy, f, up, down, padding, flip_filter, gain, ctx.hw, op=lambda *a, **k: fir(*a, r1=True, **k)), None, None
+        return _UpfirdnFn._plain(ctx, gy)
+
+    @staticmethod
+    @_first_order
+    def _plain(ctx, gy):
         f, up, down, padding, flip_filter, gain = ctx.meta
-        return _upfirdn2d_adjoint(gy, f, up, down, padding, flip_filter, gain, ctx.hw), None
+        return _upfirdn2d_adjoint(gy, f, up, down, padding, flip_filter, gain, ctx.hw), None, None
 
 
-def fir(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
-    """upfirdn2d for the discriminator: the plain call under no_grad, first-order differentiable in x (the adjoint is upfirdn2d with
-    up and down exchanged and the flipped filter, _upfirdn2d_adjoint) when x requires grad."""
+def fir(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1, r1=False):
+    """upfirdn2d for the discriminator: the plain call under no_grad, differentiable in x (the adjoint is upfirdn2d with up and down
+    exchanged and the flipped filter, _upfirdn2d_adjoint) when x requires grad: first order only, or with r1 to any order."""
     if _wants_grad(x):
-        return _UpfirdnFn.apply(x, (f, up, down, padding, flip_filter, gain))
+        return _UpfirdnFn.apply(x, (f, up, down, padding, flip_filter, gain), bool(r1))
     return upfirdn2d(x, f, up, down, padding, flip_filter, gain)
 
 
@@ -1587,11 +1664,11 @@ def _mbstd_impl(x, group, F):
     return y, sd, G
 
 
-def minibatch_std(x, group_size, num_channels=1):
-    """MinibatchStdLayer.forward (networks_stylegan2.py:854-869): x [N,C,H,W] -> [N,C+F,H,W].  Plain under no_grad, a first-order
-    autograd function when x requires grad — same forward bits."""
+def minibatch_std(x, group_size, num_channels=1, r1=False):
+    """MinibatchStdLayer.forward (networks_stylegan2.py:854-869): x [N,C,H,W] -> [N,C+F,H,W].  Plain under no_grad, an autograd function
+    when x requires grad — same forward bits; first order, or with r1 second order in a backward that autograd records."""
     if _wants_grad(x):
-        return _MbStdFn.apply(x, group_size, int(num_channels))
+        return _MbStdFn.apply(x, group_size, int(num_channels), bool(r1))
     return _mbstd_impl(x, group_size, int(num_channels))[0]
 
 
@@ -1610,18 +1687,159 @@ def mbstd_backward(x, sd, gy, G, F):
 
 class _MbStdFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, group, F):
+    def forward(ctx, x, group, F, r1=False):
         y, sd, G = _mbstd_impl(x, group, F)
         ctx.save_for_backward(x, sd)
-        ctx.G, ctx.F = G, F
+        ctx.G, ctx.F, ctx.r1 = G, F, r1
         return y
 
     @staticmethod
-    @_first_order
     def backward(ctx, gy):
+        if ctx.r1 and torch.is_grad_enabled():
+            x, sd = ctx.saved_tensors  # x is the graph's own tensor: the second-order gradient flows on into the layers below
+            gy = gy.contiguous()
+            return _R1MbStdFn.apply(gy, x, sd, ctx.G, ctx.F) + gy[:, :x.shape[1]], None, None, None
+        return _MbStdFn._plain(ctx, gy)
+
+    @staticmethod
+    @_first_order
+    def _plain(ctx, gy):
         x, sd = ctx.saved_tensors
         gy = gy.contiguous()
-        return mbstd_backward(x, sd, gy, ctx.G, ctx.F).add_(gy[:, :x.shape[1]]), None, None
+        return mbstd_backward(x, sd, gy, ctx.G, ctx.F).add_(gy[:, :x.shape[1]]), None, None, None
+
+
+# ======================================================================================================================
+# The R1 penalty: the recorded first backward of the discriminator's layers, closed under one more differentiation
+# (include/p3d_r1.h)
+# ======================================================================================================================
+def _conv2d_mask_impl(h, wk, pre, act, gain, clamp, stride, pad):
+    """p3d_conv2d_mask_f32: the tangent layer m(pre) * corr(h, wk; stride, pad) in one launch, m the mask-and-gain rule of
+    bias_act_backward.  h [N,Ci,Hi,Wi], wk [taps,Ci,Co], pre [N,Co,Ho,Wo]."""
+    h, wk, pre = _chk(h, "h"), _chk(wk, "wk"), _chk(pre, "pre")
+    idx, alpha, dg = _ACTS[act]
+    N, Ci, Hi, Wi = h.shape
+    taps, _, Co = wk.shape
+    if wk.shape[1] != Ci or tuple(pre.shape[:2]) != (N, Co):
+        raise RuntimeError("conv2d_mask: h [N,Ci,H,W], wk [taps,Ci,Co] and pre [N,Co,Ho,Wo]")
+    out = torch.empty_like(pre)
+    with _on(h.device):
+        rc = _lib.lib().p3d_conv2d_mask_f32(_p(h), N, Ci, Hi, Wi, _p(wk), taps, Co, pre.shape[2], pre.shape[3], int(stride), int(pad), _p(pre),
+                                            idx, float(alpha), float(gain if gain is not None else dg), float(clamp if clamp is not None else -1),
+                                            _p(out), _stream())
+    _lib.check(rc, "p3d_conv2d_mask_f32")
+    return out
+
+
+def mbstd_backward2(x, gy, h, G, F):
+    """p3d_mbstd_backward2_f32, the backward of mbstd_backward: x, h [N,C,H,W] (h the cotangent of mbstd_backward's result), gy
+    [N,C+F,H,W] the concatenated cotangent it was called with -> (the gradient of gy's F statistic channels [N,F,H,W], of x [N,C,H,W])."""
+    x, gy, h = _chk(x, "x"), _chk(gy, "gy"), _chk(h, "h")
+    N, Cc, H, W = x.shape
+    g_extra = torch.empty((N, F, H, W), dtype=torch.float32, device=x.device)
+    gx = torch.empty_like(x)
+    with _on(x.device):
+        rc = _lib.lib().p3d_mbstd_backward2_f32(_p(x), C.c_void_p(gy.data_ptr() + 4 * Cc * H * W), (Cc + F) * H * W, _p(h), N, Cc, H * W,
+                                                int(G), int(F), _p(g_extra), _p(gx), _stream())
+    _lib.check(rc, "p3d_mbstd_backward2_f32")
+    return g_extra, gx
+
+
+def _r1_sumsq_impl(a, b):
+    a = _chk(a, "g_image")
+    N = a.shape[0]
+    b = _chk(b, "g_raw") if b is not None else None
+    if a.ndim < 2 or a.numel() == 0 or (b is not None and (b.shape[0] != N or b.numel() == 0)):
+        raise RuntimeError("r1_penalty: g_image [N,...] and g_raw [N,...] or None, not empty")
+    out = torch.empty((N,), dtype=torch.float32, device=a.device)
+    with _on(a.device):
+        rc = _lib.lib().p3d_r1_sumsq_f32(_p(a), a.numel() // N, _p(b), b.numel() // N if b is not None else 0, N, _p(out), _stream())
+    _lib.check(rc, "p3d_r1_sumsq_f32")
+    return out
+
+
+class _R1ConvFn(torch.autograd.Function):
+    """The input gradient of one convolution layer as a function of (g_y, wk, bias), pre a constant: forward = the three steps of
+    _Conv2dActFn's plain backward (the same bits).  Backward, for the cotangent h of g_x: towards g_y the tangent layer (one launch),
+    towards wk the weight gradient with h in the input's place, towards the bias zeros (the mask's derivative is zero almost
+    everywhere; the reference's bias_act gives the same zeros, and Adam counts a zero gradient where it skips a missing one)."""
+
+    @staticmethod
+    def forward(ctx, gy, wk, bias, pre, meta, in_shape):
+        _, _, _, stride, pad = meta
+        gz, _ = _bias_act_backward_meta(pre, gy, meta)
+        ctx.meta, ctx.has_bias = meta, bias is not None
+        ctx.save_for_backward(gz, wk, pre)
+        return _conv_input_grad(gz, wk, in_shape, stride, pad)
+
+    @staticmethod
+    @_second_order
+    def backward(ctx, h):
+        gz, wk, pre = ctx.saved_tensors
+        act, gain, clamp, stride, pad = ctx.meta
+        h = h.contiguous()
+        g_gy = _conv2d_mask_impl(h, wk, pre, act, gain, clamp, stride, pad) if ctx.needs_input_grad[0] else None
+        g_wk = _conv_weight_grad(gz, h, wk.shape[0], stride, pad) if ctx.needs_input_grad[1] else None
+        g_b = torch.zeros((wk.shape[2],), dtype=h.dtype, device=h.device) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return g_gy, g_wk, g_b, None, None, None
+
+
+class _R1MaskFn(torch.autograd.Function):
+    """bias_act's backward g -> g_z as a function of (g, bias) with the output y a constant (a fully-connected layer with an
+    activation in the recorded pass): diagonal, so its own backward is the same launch on the cotangent; zeros towards the bias."""
+
+    @staticmethod
+    def forward(ctx, g, bias, y, meta):
+        ctx.meta, ctx.has_bias = meta, bias is not None
+        ctx.save_for_backward(y)
+        return _bias_act_backward_meta(y, g.contiguous(), meta)[0]
+
+    @staticmethod
+    @_second_order
+    def backward(ctx, h):
+        y, = ctx.saved_tensors
+        g_g = _bias_act_backward_meta(y, h.contiguous(), ctx.meta)[0] if ctx.needs_input_grad[0] else None
+        g_b = torch.zeros((y.shape[1],), dtype=h.dtype, device=h.device) if ctx.has_bias and ctx.needs_input_grad[1] else None
+        return g_g, g_b, None, None
+
+
+class _R1MbStdFn(torch.autograd.Function):
+    """mbstd_backward as a function of (gy, x), the deviation map a constant; its backward is p3d_mbstd_backward2_f32."""
+
+    @staticmethod
+    def forward(ctx, gy, x, sd, G, F):
+        ctx.G, ctx.F = G, F
+        ctx.save_for_backward(gy, x)
+        return mbstd_backward(x, sd, gy, G, F)
+
+    @staticmethod
+    @_second_order
+    def backward(ctx, h):
+        gy, x = ctx.saved_tensors
+        g_extra, gx = mbstd_backward2(x, gy, h.contiguous(), ctx.G, ctx.F)
+        g_gy = torch.cat([torch.zeros_like(x), g_extra], dim=1) if ctx.needs_input_grad[0] else None
+        return g_gy, (gx if ctx.needs_input_grad[1] else None), None, None, None
+
+
+class _R1PenaltyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g_image, g_raw):
+        ctx.save_for_backward(g_image, g_raw)
+        return _r1_sumsq_impl(g_image, g_raw)
+
+    @staticmethod
+    def backward(ctx, cot):
+        g_image, g_raw = ctx.saved_tensors
+        scale = lambda g: (2 * cot).reshape(-1, *([1] * (g.ndim - 1))) * g
+        return scale(g_image), (scale(g_raw) if g_raw is not None else None)
+
+
+def r1_penalty(g_image, g_raw=None):
+    """The R1 penalty of loss_orthocondA.py:727 / :732 per sample: sum g_image^2 (+ sum g_raw^2) over everything but the batch axis, in
+    one launch of p3d_r1_sumsq_f32; its gradient is 2 * cotangent[n] * g."""
+    if _wants_grad(g_image, g_raw):
+        return _R1PenaltyFn.apply(g_image, g_raw)
+    return _r1_sumsq_impl(g_image, g_raw)
 
 
 # ======================================================================================================================

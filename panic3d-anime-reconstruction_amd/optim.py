@@ -9,7 +9,7 @@ include/p3d_optim.h):
 
 Why the step lives in this package: every parameter-derived cache here (memo.py) is keyed on a tensor's `_version`, and the kernel
 writes through raw pointers.  ops.adam_ema_step bumps the version of everything it wrote, so no caller needs `clear_memo()` after a
-step.  Not here: the R1 penalty, LPIPS, the augment pipe's module (its operator is ops.augment_apply), the data loader and the loop itself.
+step.  Not here: the R1 penalty (loss.py's Dreg / Dboth with DualDiscriminator.set_r1_grad()), LPIPS, the augment pipe's module (its operator is ops.augment_apply), the data loader and the loop itself.
 """
 import math
 import weakref

@@ -79,7 +79,7 @@ class FullyConnectedLayer(_CacheFree):
                     b = b * self.bias_gain
             if self.activation == "linear":
                 return torch.addmm(b.unsqueeze(0), x, w.t()) if b is not None else x.matmul(w.t())
-            return _FcActFn.apply(x, w, b, self.activation)
+            return _FcActFn.apply(x, w, b, self.activation, getattr(self, "r1_grad", False))
         w, b = self._scaled(x.dtype)
         if self.activation == "linear" and b is not None:
             return torch.addmm(b.unsqueeze(0), x, w.t())
@@ -91,21 +91,27 @@ class _FcActFn(torch.autograd.Function):
     p3d_bias_act_backward_f32 with the mask taken from the OUTPUT (no pre-activation is kept), the [N,C] result seen as [N,C,1,1]."""
 
     @staticmethod
-    def forward(ctx, x, w, b, act):
+    def forward(ctx, x, w, b, act, r1=False):
         y = ops.bias_act(x.matmul(w.t()).contiguous(), b, act=act)
-        ctx.save_for_backward(x, w, y)
-        ctx.act, ctx.has_bias = act, b is not None
+        ctx.save_for_backward(x, w, y, *([b] if r1 and b is not None else []))
+        ctx.act, ctx.has_bias, ctx.r1 = act, b is not None, r1
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, w, y = ctx.saved_tensors
+        x, w, y = ctx.saved_tensors[:3]
         idx, alpha, gain = ops._ACTS[ctx.act]
-        gz, gb, _ = ops.bias_act_backward(y, g.contiguous(), idx, alpha, gain, None)
+        if ctx.r1 and torch.is_grad_enabled():
+            # the discriminator's recorded backward (DualDiscriminator.set_r1_grad, DESIGN.md §4.21): the same launch inside a Function
+            # of (g, bias), the products torch's own, so that the R1 penalty's backward reaches g, w and x; same bits as below
+            gz = ops._R1MaskFn.apply(g, ctx.saved_tensors[3] if ctx.has_bias else None, y.detach(), (ctx.act, gain, None))
+            gb = gz
+        else:
+            gz, gb, _ = ops.bias_act_backward(y, g.contiguous(), idx, alpha, gain, None)
         gx = gz.matmul(w) if ctx.needs_input_grad[0] else None
         gw = gz.t().matmul(x) if ctx.needs_input_grad[1] else None
         gbias = gb.sum(dim=0) if ctx.has_bias and ctx.needs_input_grad[2] else None  # [N,C] sums over "pixels" -> column sums
-        return gx, gw, gbias, None
+        return gx, gw, gbias, None, None
 
 
 class MappingNetwork(torch.nn.Module):
