@@ -8,7 +8,7 @@ SO = os.path.join(HERE, "libpanic3d_hip.so")
 SOURCES = ["p3d_kernels.hip", "p3d_synthesis.hip", "p3d_conv_plain.hip", "p3d_conv_up.hip", "p3d_conv_up4.hip", "p3d_fir.hip", "p3d_torgb.hip",
            "p3d_mcubes.hip", "p3d_paste.hip", "p3d_render_grad.hip", "p3d_synthesis_grad.hip", "p3d_paste_grad.hip", "p3d_discriminator.hip", "p3d_loss.hip",
            "p3d_optim.hip", "p3d_lpips.hip", "p3d_encoder.hip", "p3d_metrics.hip", "p3d_rmline.hip", "p3d_rmline_grad.hip", "p3d_clip.hip",
-           "p3d_augment.hip", "p3d_r1.hip"]
+           "p3d_augment.hip", "p3d_r1.hip", "p3d_augment_tail.hip"]
 HEADERS = ["p3d_math.hpp", "p3d_decode.hpp", "p3d_ray_phases.hpp", "p3d_lds_layout.hpp", "p3d_render_plan.hpp", "p3d_cull_band.hpp", "p3d_phase_timing.hpp", "p3d_importance.hpp", "p3d_conv_common.hpp", "p3d_conv_plan.hpp", "p3d_conv_stage.hpp", "p3d_torgb_plan.hpp", os.path.join("..", "..", "include", "panic3d_hip.h"),
            os.path.join("..", "..", "include", "p3d_numerics.h"), os.path.join("..", "..", "include", "p3d_mc_table.h"),
            "p3d_decode_grad.hpp", os.path.join("..", "..", "include", "p3d_render_grad.h"),
@@ -22,7 +22,7 @@ HEADERS = ["p3d_math.hpp", "p3d_decode.hpp", "p3d_ray_phases.hpp", "p3d_lds_layo
            "p3d_rmline_tile.hpp", "p3d_rmline_grad_plan.hpp", os.path.join("..", "..", "include", "p3d_rmline_grad.h"),
            "p3d_clip_plan.hpp", os.path.join("..", "..", "include", "p3d_clip.h"),
            "p3d_augment_plan.hpp", os.path.join("..", "..", "include", "p3d_augment.h"), os.path.join("..", "..", "include", "p3d_augment_table.h"),
-           os.path.join("..", "..", "include", "p3d_r1.h")]
+           os.path.join("..", "..", "include", "p3d_r1.h"), os.path.join("..", "..", "include", "p3d_augment_tail.h")]
 # -fno-slp-vectorize: v_pk_fma_f32 runs at ~0.4x the flop rate of v_fma_f32 on gfx950 (tools/ubench/valu_rates.hip).
 # -ffp-contract=off: the arithmetic contract (include/p3d_numerics.h) names every fma explicitly.
 # -pragma-unroll-threshold: k_render<96,...>'s twelve inverse-CDF batches must unroll completely (their results live in a

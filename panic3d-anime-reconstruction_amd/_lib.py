@@ -288,6 +288,13 @@ R1_SIGNATURES = {
     "p3d_mbstd_backward2_f32": (_I, [_P, _P, _L, _P, _I, _I, _L, _I, _I, _P, _P, _P]),
     "p3d_r1_sumsq_f32": (_I, [_P, _L, _P, _L, _I, _P, _P]),
 }
+# symbol -> (restype, argtypes); every function include/p3d_augment_tail.h declares (the augmentation pipe's filter, noise and cutout, and the adjoint)
+AUGMENT_TAIL_SIGNATURES = {
+    "p3d_augment_tail_plan": (_I, [_I, C.POINTER(C.c_int), _I]),
+    "p3d_augment_tail_f32": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "p3d_augment_tail_adjoint_f32": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+}
+P3D_TAIL_MAX_TAPS, P3D_TAIL_TILE_W, P3D_TAIL_MAX_SIDE, P3D_TAIL_LDS_BYTES = 63, 64, 32768, 81920  # include/p3d_augment_tail.h
 P3D_AUG_PLAN_AUTO, P3D_AUG_PLAN_TILE, P3D_AUG_PLAN_STAGED, P3D_AUG_TILE, P3D_AUG_LDS_BYTES, P3D_AUG_MAX_SIDE = 0, 1, 2, 16, 65536, 16384  # include/p3d_augment.h
 P3D_CLIP_KC, P3D_CLIP_CUS, P3D_CLIP_TILE_64, P3D_CLIP_TILE_32, P3D_CLIP_MAX_SPLIT, P3D_CLIP_XCDS = 64, 256, 1, 2, 255, 8   # include/p3d_clip.h
 P3D_CLIP_GELU, P3D_CLIP_PATCH, P3D_CLIP_HEAD_DIM, P3D_CLIP_MAX_T, P3D_CLIP_MAX_SIDE, P3D_CLIP_MAX_S = 1, 2, 64, 64, 16384, 4096  # include/p3d_clip.h
@@ -327,7 +334,8 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(SYN_GRAD_SIGNATURES.items()) \
                 + list(PASTE_GRAD_SIGNATURES.items()) + list(DISC_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
                 + list(LPIPS_SIGNATURES.items()) + list(ENCODER_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(RMLINE_SIGNATURES.items()) \
-                + list(CLIP_SIGNATURES.items()) + list(RMLINE_GRAD_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(R1_SIGNATURES.items()):
+                + list(CLIP_SIGNATURES.items()) + list(RMLINE_GRAD_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(R1_SIGNATURES.items()) \
+                + list(AUGMENT_TAIL_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = L.p3d_abi_version()

@@ -3689,3 +3689,90 @@ def augment_apply_adjoint(g, G_inv, margins=None, C=None, plan=None):
     if _wants_grad(g):
         return _AugmentFn.apply(g, geom, True)
     return _augment_impl(g, geom, True)
+
+
+# ---- the augmentation pipe's tail (include/p3d_augment_tail.h) ---------------------------------------------------------
+class AugmentTail:
+    """What one call of the tail needs besides the image, on the device: taps [N, K] (or None), z [N, C, H, W] and sigma [N] (both or
+    neither), rect [N, 4] int32 = (x0, x1, y0, y1) (or None)."""
+
+    def __init__(self, taps=None, z=None, sigma=None, rect=None):
+        self.taps = _chk(taps, "taps") if taps is not None else None
+        self.z = _chk(z, "z") if z is not None else None
+        self.sigma = _chk(sigma, "sigma").reshape(-1) if sigma is not None else None
+        self.rect = _chk(rect, "rect", torch.int32) if rect is not None else None
+        if (self.z is None) != (self.sigma is None):
+            raise RuntimeError("augment_tail: the noise needs both z and sigma")
+        if self.taps is not None and (self.taps.ndim != 2 or self.taps.shape[1] % 2 == 0 or self.taps.shape[1] > _lib.P3D_TAIL_MAX_TAPS):
+            raise RuntimeError(f"augment_tail: taps must be [N, K] with K odd and at most {_lib.P3D_TAIL_MAX_TAPS}")
+
+
+def augment_tail_plan(K):
+    """(the forward's tile height, its LDS bytes, the adjoint's tile height, its LDS bytes) for K taps; the tile is P3D_TAIL_TILE_W wide."""
+    out = (C.c_int * 4)()
+    _lib.check(_lib.lib().p3d_augment_tail_plan(int(K), out, 4), "p3d_augment_tail_plan")
+    return tuple(out)
+
+
+def _augment_tail_impl(x, tail, adjoint):
+    x = _chk(x, "images")
+    if x.ndim != 4:
+        raise RuntimeError("augment_tail: images must be [N, C, H, W]")
+    N, Cc, H, W = x.shape
+    for t, name, shape in ((tail.taps, "taps", None), (tail.z, "z", tuple(x.shape)), (tail.sigma, "sigma", (N,)), (tail.rect, "rect", (N, 4))):
+        if t is None:
+            continue
+        if t.device != x.device or t.shape[0] != N or (shape is not None and tuple(t.shape) != shape):
+            raise RuntimeError(f"augment_tail: {name} must be on the images' device with their batch" + (f", shaped {shape}" if shape else ""))
+    K = tail.taps.shape[1] if tail.taps is not None else 0
+    if K // 2 >= min(H, W) and K:
+        raise RuntimeError(f"augment_tail: {K} taps reflect {K // 2} pixels, beyond an image of {H} x {W} (P3D_E_RANGE)")
+    y = torch.empty_like(x)
+    L = _lib.lib()
+    with _on(x.device):
+        if adjoint:
+            rc = L.p3d_augment_tail_adjoint_f32(_p(x), _p(tail.taps), K, _p(tail.rect), N, Cc, H, W, _p(y), _stream())
+        else:
+            rc = L.p3d_augment_tail_f32(_p(x), _p(tail.taps), K, _p(tail.z), _p(tail.sigma), _p(tail.rect), N, Cc, H, W, _p(y), _stream())
+    _lib.check(rc, "p3d_augment_tail_adjoint_f32" if adjoint else "p3d_augment_tail_f32")
+    return y
+
+
+class _AugmentTailFn(torch.autograd.Function):
+    """The tail is affine in the image (its offset the noise) and its adjoint linear: each is the other's backward, called through the
+    public functions again, so the pair is differentiable to any order with no further kernel (the pattern of _AugmentFn)."""
+
+    @staticmethod
+    def forward(ctx, x, tail, adjoint):
+        ctx.tail, ctx.adjoint = tail, adjoint
+        return _augment_tail_impl(x, tail, adjoint)
+
+    @staticmethod
+    def backward(ctx, g):
+        t = ctx.tail
+        if ctx.adjoint:  # the adjoint's backward is the tail without its noise
+            return augment_tail(g, AugmentTail(t.taps, None, None, t.rect)), None, None
+        return augment_tail_adjoint(g, t), None, None
+
+
+def _augment_tail_args(taps, z, sigma, rect):
+    return taps if isinstance(taps, AugmentTail) else AugmentTail(taps, z, sigma, rect)
+
+
+def augment_tail(images, taps=None, z=None, sigma=None, rect=None):
+    """p3d_augment_tail_f32 on images [N, C, H, W]: the per-sample separable filter taps [N, K] on the reflected image (rows, then
+    columns), + sigma [N] * z [N, C, H, W], then zero inside rect [N, 4] int32 = (x0, x1, y0, y1); every stage optional, all on the
+    device.  taps may also be a ready AugmentTail.  Differentiable in the images to any order, with no gradient to taps, sigma or z;
+    the same bits with and without autograd."""
+    tail = _augment_tail_args(taps, z, sigma, rect)
+    if _wants_grad(images):
+        return _AugmentTailFn.apply(images, tail, False)
+    return _augment_tail_impl(images, tail, False)
+
+
+def augment_tail_adjoint(g, taps=None, z=None, sigma=None, rect=None):
+    """p3d_augment_tail_adjoint_f32: the transpose of augment_tail's linear part (the noise does not enter), applied to g [N, C, H, W]."""
+    tail = _augment_tail_args(taps, z, sigma, rect)
+    if _wants_grad(g):
+        return _AugmentTailFn.apply(g, tail, True)
+    return _augment_tail_impl(g, tail, True)
