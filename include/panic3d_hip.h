@@ -70,6 +70,9 @@ extern "C" {
                                      * 48 / 96 fine samples) the final pass decodes densities only: wsum / depth bit-identical to the full
                                      * launch's, out_feat / out_xyz LEFT UNWRITTEN (still valid pointers: elsewhere the hint is ignored and
                                      * the full kernel fills them). */
+#define P3D_FLAG_GENERIC_TAPS 131072 /* p3d_render_f32, a TEST SWITCH: k_render keeps the generic gather set-up (every tap range-tested and
+                                      * addressed on its own) also where the launch's crop would let it take the interior form
+                                      * (p3d_render_interior_taps, csrc/p3d_render_plan.hpp).  Same bits either way: tests, A/B timing. */
 #define P3D_FLAG_SHARED_PLANES 64 /* planes holds ONE image [1][3][H][W][32] shared by all N batches of rays / points (many
                                     views of one subject in one launch; the reference would pass planes.expand(N, ...)) */
 
@@ -182,6 +185,11 @@ int p3d_render_rng_f32(const float* planes_nhwc, int N, int H, int W, const floa
  * wave-level decode steps with every sample decoded, grid, block, dynamic LDS bytes.  Returns 0, or the P3D_E_* code that
  * p3d_render_limits_f32 returns for these arguments (with valid buffers); P3D_E_ARG for opts == NULL, out == NULL or cap < 6. */
 int p3d_render_plan_info(int N, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits, int64_t* out, int cap);
+
+/* ... and whether that launch sets its gathers up in the interior form (1) or the generic one (0): the interior form needs H x W
+ * planes whose taps the crop keeps inside (p3d_render_interior_taps, csrc/p3d_render_plan.hpp), no P3D_FLAG_GENERIC_TAPS, and a
+ * launch that takes k_render with the early-outs on.  Same bits either way.  Negative: the P3D_E_* code as above. */
+int p3d_render_taps_info(int N, int H, int W, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits);
 
 /* sample_stratified (renderer.py:303-326, numeric ray_start/ray_end branch).  jitter, out [NR][S]. */
 int p3d_sample_stratified_f32(float ray_start, float ray_end, float depth_delta, int S, const float* jitter, int64_t NR,

@@ -13,6 +13,7 @@ P3D_FLAG_DISPARITY = 4096
 P3D_FLAG_PAIR16 = 16384
 P3D_FLAG_QUAD8 = 32768
 P3D_FLAG_WEIGHTS_ONLY = 65536
+P3D_FLAG_GENERIC_TAPS = 131072  # test switch: k_render keeps the generic gather set-up (include/panic3d_hip.h)
 P3D_MAX_S = 192
 P3D_ABI_VERSION = 9  # include/panic3d_hip.h; lib() refuses a library built for another version
 
@@ -120,6 +121,7 @@ SIGNATURES = {
     "p3d_render_rng_f32": (_I, [_P, _I, _I, _I, _P, _P, _L, _I, C.c_uint64, _P, _P, _P, _P, _P, _P, C.POINTER(Opts), _P, _P, _P, _P, _P,
                                 _Z, C.POINTER(Dumps), _P]),
     "p3d_render_plan_info": (_I, [_I, _L, _I, C.POINTER(Opts), _I, _I, C.POINTER(C.c_int64), _I]),
+    "p3d_render_taps_info": (_I, [_I, _I, _I, _L, _I, C.POINTER(Opts), _I, _I]),
     "p3d_sample_stratified_f32": (_I, [_F, _F, _F, _I, _P, _L, _P, _P]),
     "p3d_composite_workspace_bytes": (_Z, [_L, _I, _I]),
     "p3d_depth_minmax_f32": (_I, [_P, _L, _P, _P, _Z, _P]),

@@ -380,11 +380,112 @@ P3D_DEV f32x16 p3d_quad_transpose(const f32x16& in) {
 }
 #endif  // P3D_QUAD_EXCHANGE
 
+// ---- the interior form of the quad-cooperative gather set-up (INTERIOR; the launch decides: p3d_render_interior_taps) -----------
+// For launches whose crop keeps every tap of the x and z axes inside the W x W planes, at call sites where a live lane is never a
+// cropped one (k_render's early-outs).  What the generic set-up computes per plane and per tap it computes per axis and per texel row:
+//   * one coordinate chain per AXIS (ix, floor, the two fractions, the integer), shared by the planes that use the axis (W == H);
+//   * no range test on x and z beyond  okx = live && |px| <= crop_limit,  okz = live && |pz| <= crop_limit  (false for a NaN, which
+//     the generic `inr` turns into zero features too); y, which nothing crops, keeps `inr` (yin) and its two tap tests;
+//   * no select on a weight: a lane whose plane is out (not okx / okz / yin) has that plane's addresses diverted to
+//     P3D_OOB_OFFSET, so its taps load zeros, and ONE select per axis puts 0 in place of a coordinate that is out, so that its
+//     weights are finite and non-negative: w * (+0) accumulates to the +0 the generic set-up's 0 * 0 gives;
+//   * one address per quad member and texel ROW (plane 0, whose rows y can leave) or per texel (plane 1, and plane 2 of plane_mode 0)
+//     or per texel COLUMN (plane 2 of plane_mode 1: y is its column), the neighbours through the load's immediate offset (+128, the
+//     next column) and its scalar offset (+row, wave-uniform).  P3D_OOB_OFFSET + row + 128 + 63 neither wraps nor comes back in range.
+// The weights, the taps' values and the fold are the generic ones, operand for operand: no output bit differs.
+struct P3dAxisTaps { float w0, w1; int i0; };
+P3D_DEV P3dAxisTaps p3d_axis_taps(float i, bool ok) {
+    const float is = ok ? i : 0.0f;
+    const float f = __builtin_floorf(is);
+    P3dAxisTaps a;
+    a.w1 = is - f;
+    a.w0 = 1.0f - a.w1;
+    a.i0 = (int)f;
+    return a;
+}
+// tap registers as p3d_load16_quad; a[r] = the address of quad member r's texel piece, IMM / soff = the neighbour
+template <int IMM, typename RSRC>
+P3D_DEV f32x16 p3d_load16_quad_at(RSRC rs, const uint32_t a[4], uint32_t soff) {
+    const i32x4 qa = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[0] + (uint32_t)IMM), (int)soff, 0);
+    const i32x4 qb = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[1] + (uint32_t)IMM), (int)soff, 0);
+    const i32x4 qc = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[2] + (uint32_t)IMM), (int)soff, 0);
+    const i32x4 qd = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[3] + (uint32_t)IMM), (int)soff, 0);
+    const f32x4 fa = __builtin_bit_cast(f32x4, qa), fb = __builtin_bit_cast(f32x4, qb), fc = __builtin_bit_cast(f32x4, qc),
+                fd = __builtin_bit_cast(f32x4, qd);
+    f32x16 v;
+    v.s0 = fa.x; v.s1 = fa.y; v.s2 = fa.z; v.s3 = fa.w;
+    v.s4 = fb.x; v.s5 = fb.y; v.s6 = fb.z; v.s7 = fb.w;
+    v.s8 = fc.x; v.s9 = fc.y; v.sa = fc.z; v.sb = fc.w;
+    v.sc = fd.x; v.sd = fd.y; v.se = fd.z; v.sf = fd.w;
+    return v;
+}
+P3D_DEV void p3d_quad_addresses(uint32_t base, uint32_t a[4]) {
+    const uint32_t piece = ((uint32_t)__lane_id() & 3u) * 16u;
+    a[0] = p3d_quad_u<0x00>(base) + piece; a[1] = p3d_quad_u<0x55>(base) + piece;
+    a[2] = p3d_quad_u<0xaa>(base) + piece; a[3] = p3d_quad_u<0xff>(base) + piece;
+}
+template <typename RSRC>
+P3D_DEV f32x16 p3d_gather_features_interior(RSRC rs, const P3dPlaneGeom& g, const P3dDecodeCfg& cfg, float px, float py, float pz,
+                                            bool live) {
+    const int h = __lane_id() >> 5;
+    const uint32_t chan_off = (uint32_t)h * 64u;
+    const float qx = px * cfg.coord_scale, qy = py * cfg.coord_scale, qz = pz * cfg.coord_scale;  // renderer.py:77
+    // W == H: halfW and fW stand for both
+    const float ix = (qx + 1.0f) * g.halfW - 0.5f, iy = (qy + 1.0f) * g.halfW - 0.5f, iz = (qz + 1.0f) * g.halfW - 0.5f;
+    const bool okx = live && __builtin_fabsf(px) <= cfg.crop_limit, okz = live && __builtin_fabsf(pz) <= cfg.crop_limit;
+    const bool yin = live && (iy > -1.0f) && (iy < g.fW);
+    const P3dAxisTaps X = p3d_axis_taps(ix, okx), Y = p3d_axis_taps(iy, yin), Z = p3d_axis_taps(iz, okz);
+    const bool ylo = Y.i0 >= 0, yhi = Y.i0 + 1 < g.W;  // y's nw / se tap inside
+    const uint32_t row = (uint32_t)g.W * 128u;
+    float wg[12];
+    // plane 0 = (x, y): rows y0 and y0 + 1, each in or out
+    wg[0] = Y.w0 * X.w0; wg[1] = Y.w0 * X.w1; wg[2] = Y.w1 * X.w0; wg[3] = Y.w1 * X.w1;
+    const uint32_t b0 = chan_off + (uint32_t)((Y.i0 * g.W + X.i0) * 128);
+    const bool in0 = okx && yin;
+    const uint32_t b0lo = (in0 && ylo) ? b0 : P3D_OOB_OFFSET, b0hi = (in0 && yhi) ? b0 + row : P3D_OOB_OFFSET;
+    // plane 1 = (x, z): all four taps in, or the lane out
+    wg[4] = Z.w0 * X.w0; wg[5] = Z.w0 * X.w1; wg[6] = Z.w1 * X.w0; wg[7] = Z.w1 * X.w1;
+    const uint32_t b1 = (okx && okz) ? g.plane_bytes + chan_off + (uint32_t)((Z.i0 * g.W + X.i0) * 128) : P3D_OOB_OFFSET;
+    // plane 2 = (z, x), or (y, z) with plane_mode (wave-uniform): columns c0 and c0 + 1, each in or out
+    uint32_t b2a, b2b;
+    if (cfg.plane_mode) {
+        wg[8] = Z.w0 * Y.w0; wg[9] = Z.w0 * Y.w1; wg[10] = Z.w1 * Y.w0; wg[11] = Z.w1 * Y.w1;
+        const uint32_t b2 = 2u * g.plane_bytes + chan_off + (uint32_t)((Z.i0 * g.W + Y.i0) * 128);
+        const bool in2 = okz && yin;
+        b2a = (in2 && ylo) ? b2 : P3D_OOB_OFFSET;
+        b2b = (in2 && yhi) ? b2 + 128u : P3D_OOB_OFFSET;
+    } else {
+        wg[8] = X.w0 * Z.w0; wg[9] = X.w0 * Z.w1; wg[10] = X.w1 * Z.w0; wg[11] = X.w1 * Z.w1;
+        b2a = (okx && okz) ? 2u * g.plane_bytes + chan_off + (uint32_t)((X.i0 * g.W + Z.i0) * 128) : P3D_OOB_OFFSET;
+        b2b = b2a + 128u;
+    }
+    // the members' addresses are made where the fold first asks for them (k is a constant of the unrolled fold): five sets of four
+    uint32_t a0[4], a1[4], a2a[4], a2b[4];
+    return p3d_quad_transpose(p3d_fold_taps<true>(wg, [&](int k) __attribute__((always_inline)) {
+        switch (k) {
+        case 0: p3d_quad_addresses(b0lo, a0); return p3d_load16_quad_at<0>(rs, a0, 0u);
+        case 1: return p3d_load16_quad_at<128>(rs, a0, 0u);
+        case 2: p3d_quad_addresses(b0hi, a0); return p3d_load16_quad_at<0>(rs, a0, 0u);
+        case 3: return p3d_load16_quad_at<128>(rs, a0, 0u);
+        case 4: p3d_quad_addresses(b1, a1); return p3d_load16_quad_at<0>(rs, a1, 0u);
+        case 5: return p3d_load16_quad_at<128>(rs, a1, 0u);
+        case 6: return p3d_load16_quad_at<0>(rs, a1, row);
+        case 7: return p3d_load16_quad_at<128>(rs, a1, row);
+        case 8: p3d_quad_addresses(b2a, a2a); return p3d_load16_quad_at<0>(rs, a2a, 0u);
+        case 9: p3d_quad_addresses(b2b, a2b); return p3d_load16_quad_at<0>(rs, a2b, 0u);
+        case 10: return p3d_load16_quad_at<0>(rs, a2a, row);
+        default: return p3d_load16_quad_at<0>(rs, a2b, row);
+        }
+    }));
+}
+
 // This lane's 16 interpolated feature channels (16h .. 16h+15) of the sample at (px,py,pz): the three bilinear plane samples
 // and their mean (renderer.py:68-81, triplane.py:530), gathered straight from the planes (per-lane L1 gathers).
-template <bool QUADG = false, typename RSRC>
+template <bool QUADG = false, bool INTERIOR = false, typename RSRC>
 P3D_DEV f32x16 p3d_gather_features(RSRC rs, const P3dPlaneGeom& g, const P3dDecodeCfg& cfg, float px, float py, float pz,
                                    bool live) {
+    static_assert(!INTERIOR || QUADG, "the interior set-up exists for the quad-cooperative gather");
+    if constexpr (INTERIOR) return p3d_gather_features_interior(rs, g, cfg, px, py, pz, live);
     const int h = __lane_id() >> 5;
     const uint32_t chan_off = (uint32_t)h * 64u;
     float qx = px * cfg.coord_scale, qy = py * cfg.coord_scale, qz = pz * cfg.coord_scale;  // renderer.py:77
@@ -597,10 +698,12 @@ template <bool WANT_RGB, bool LAZY = false>
 P3D_DEV bool p3d_decode_features(const float* lds, const P3dDecodeCfg& cfg, const f32x16& X, float px, float pz, float& sigma_out,
                                  f32x16& rgb, bool live = true);
 
-template <bool WANT_RGB, bool QUADG = false, bool LAZY = false, typename RSRC>
+// INTERIOR: the interior gather set-up (p3d_gather_features_interior): only where the launch's plan allows it and a live lane is
+// never a cropped one
+template <bool WANT_RGB, bool QUADG = false, bool LAZY = false, bool INTERIOR = false, typename RSRC>
 P3D_DEV bool p3d_decode_wave(const float* lds, RSRC rs, const P3dPlaneGeom& g, const P3dDecodeCfg& cfg, float px,
                              float py, float pz, float& sigma_out, f32x16& rgb, bool live = true) {
-    const f32x16 X = p3d_gather_features<QUADG>(rs, g, cfg, px, py, pz, live);
+    const f32x16 X = p3d_gather_features<QUADG, INTERIOR>(rs, g, cfg, px, py, pz, live);
     return p3d_decode_features<WANT_RGB, LAZY>(lds, cfg, X, px, pz, sigma_out, rgb, live);
 }
 
@@ -729,10 +832,10 @@ template <bool WANT_RGB, bool LAZY = false, bool GUARD = false>
 P3D_DEV bool p3d_decode_features_fast(const float* lds, const P3dDecodeCfg& cfg, const f32x16& X, float px, float pz, float& sigma_out,
                                       f32x16& rgb, bool live = true);
 
-template <bool WANT_RGB = true, bool QUADG = false, bool LAZY = false, bool GUARD = false, typename RSRC>
+template <bool WANT_RGB = true, bool QUADG = false, bool LAZY = false, bool GUARD = false, bool INTERIOR = false, typename RSRC>
 P3D_DEV bool p3d_decode_wave_fast(const float* lds, RSRC rs, const P3dPlaneGeom& g, const P3dDecodeCfg& cfg, float px,
                                   float py, float pz, float& sigma_out, f32x16& rgb, bool live = true) {
-    const f32x16 X = p3d_gather_features<QUADG>(rs, g, cfg, px, py, pz, live);
+    const f32x16 X = p3d_gather_features<QUADG, INTERIOR>(rs, g, cfg, px, py, pz, live);
     return p3d_decode_features_fast<WANT_RGB, LAZY, GUARD>(lds, cfg, X, px, pz, sigma_out, rgb, live);
 }
 

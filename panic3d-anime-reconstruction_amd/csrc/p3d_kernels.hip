@@ -325,9 +325,17 @@ __global__ __launch_bounds__(P3D_WG, 2) void k_decode_features(DecodeFeatParams 
 // TCG is a template parameter of its own (default: on wherever it can be): the plan turns it OFF for the launches whose coarse
 // depths are not the plain stratified spacing — per-ray limits (ray_start = 'auto') and disparity spacing — which p3d_stratified_fixed()
 // does not know (with TCG derived from (NF, DUMP, EARLY) alone those launches silently rendered the fixed spacing).
-template <int NF, bool DUMP, bool FAST, bool EARLY, bool TCG = p3d_render_tcg(NF, DUMP, EARLY)>
+// INTERIOR (EARLY only; the launch decides: p3d_render_interior_taps, p3d_render_plan.hpp): the crop keeps every tap of the x and z
+// axes inside the planes, and with the early-outs a lane is decoded only when its sample is not cropped — the coarse loops' `live`
+// and the walk's `live = have && !known` both exclude a cropped sample — so those decodes set their gathers up in the interior form
+// (p3d_decode.hpp).  The guard decodes fetch the colours of consumed samples, cropped ones included: they keep the generic form, as
+// does every instantiation without the early-outs.  A template parameter and not a wave-uniform branch: the two set-ups feed the
+// fold through different loads, a branch would have to duplicate the fold and the transpose in every decode of the kernel, and the
+// instantiation a launch does not take costs it nothing.
+template <int NF, bool DUMP, bool FAST, bool EARLY, bool TCG = p3d_render_tcg(NF, DUMP, EARLY), bool INTERIOR = false>
 __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) void k_render(RenderParams p) {
     static_assert(!(DUMP && EARLY), "dumps need every sample decoded");
+    static_assert(!INTERIOR || EARLY, "without the early-outs cropped samples are decoded: the generic gather set-up");
     static_assert(!TCG || p3d_render_tcg(NF, DUMP, EARLY), "TCG exists only for the production 96-key kernel");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     P3D_PHASE_START();
@@ -478,7 +486,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     const bool skip = __builtin_amdgcn_ballot_w64(live) == 0;
                     if (!skip) {
                         f32x16 dummy;
-                        p3d_decode_wave<false, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
+                        p3d_decode_wave<false, true, false, INTERIOR>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
                     }
                     mword |= (cropped || (live && sigma == P3D_SIGMA_MASKED)) ? (1u << (i & 31)) : 0u;
                     if ((i & 31) == 31 || i == Sc - 1) {  // wave-uniform
@@ -503,7 +511,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             }
             if (!skip) {
                 f32x16 dummy;
-                p3d_decode_wave<false, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
+                p3d_decode_wave<false, true, false, INTERIOR>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, dummy, live);
             }
             if (early) {  // a lane whose gathers were suppressed (dead ray) decoded garbage: its sample is NOT known to be masked
                 mword |= (cropped || (live && sigma == P3D_SIGMA_MASKED)) ? (1u << (i & 31)) : 0u;
@@ -825,8 +833,8 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             bool skipped = true;
             if (__builtin_amdgcn_ballot_w64(live) != 0) {
                 bool have_rgb;  // EARLY: colour on demand (p3d_decode.hpp, LAZY): a step whose live samples are all masked has none
-                if constexpr (FAST) have_rgb = p3d_decode_wave_fast<true, true, EARLY, true>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
-                else have_rgb = p3d_decode_wave<true, true, EARLY>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
+                if constexpr (FAST) have_rgb = p3d_decode_wave_fast<true, true, EARLY, true, INTERIOR>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
+                else have_rgb = p3d_decode_wave<true, true, EARLY, INTERIOR>(lds, cx.rs, cx.g, cx.cfg, px, py, pz, sigma, rgb, live);
                 if constexpr (!DUMP) ndec += 1;
                 skipped = !live || !have_rgb;  // per lane: a lane whose gathers were suppressed has no colour
                 if (known) sigma = P3D_SIGMA_MASKED;
@@ -1531,6 +1539,14 @@ int p3d_render_plan_info(int N, int64_t R, int ray_tile_w, const p3d_opts* opts,
     return P3D_OK;
 }
 
+int p3d_render_taps_info(int N, int H, int W, int64_t R, int ray_tile_w, const p3d_opts* opts, int has_dumps, int has_ray_limits) {
+    if (!opts) return P3D_E_ARG;
+    if (H <= 0 || W <= 0) return P3D_E_RANGE;
+    const RenderPlan pl = p3d_render_plan(N, R, ray_tile_w, *opts, has_dumps != 0, has_ray_limits != 0);
+    if (pl.err) return pl.err;
+    return p3d_render_plan_has_interior(pl) && p3d_render_interior_taps(H, W, *opts) ? 1 : 0;
+}
+
 int p3d_render_f32(const float* planes, int N, int H, int W, const float* rays_o, const float* rays_d, int64_t R,
                    int ray_tile_w, const float* jitter, const float* u, const float* w0, const float* b0,
                    const float* w1, const float* b1, const p3d_opts* opts, float* out_feat, float* out_depth,
@@ -1597,6 +1613,7 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     p.cfg = make_cfg(opts);
     p.tile_w = pl.tile_w; p.tiles_x = pl.tiles_x; p.tiles_per_img = pl.tiles_per_img; p.ntiles = pl.ntiles;
     p.lds_rows = pl.lds_rows; p.order = pl.order;
+    const bool interior = p3d_render_plan_has_interior(pl) && p3d_render_interior_taps(H, W, *opts);  // which gather set-up k_render runs
     hipLaunchKernelGGL(k_minmax_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, p.gminmax, p.per_view_clamp ? N : 0);
     auto launch = [&](void (*kernel)(RenderParams)) {
         hipError_t e = p3d_ensure_dynamic_lds(kernel, pl.lds_bytes);
@@ -1613,8 +1630,13 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
             switch (pl.kernel) {
             case RenderKernel::DUMP: return launch(k_render<NF, true, F, false>);
             case RenderKernel::PLAIN: return launch(k_render<NF, false, F, false>);
-            case RenderKernel::EARLY_TCG: return launch(k_render<NF, false, F, true>);  // (NF == 96 only: the default TCG of that instantiation)
-            case RenderKernel::EARLY: return launch(k_render<NF, false, F, true, false>);
+            // (EARLY_TCG: NF == 96 only, the default TCG of that instantiation)
+            case RenderKernel::EARLY_TCG: return interior ? launch(k_render<NF, false, F, true, p3d_render_tcg(NF, false, true), true>)
+                                                          : launch(k_render<NF, false, F, true>);
+            case RenderKernel::EARLY:
+                if constexpr (p3d_render_nf_has_interior(NF, false))
+                    if (interior) return launch(k_render<NF, false, F, true, false, true>);
+                return launch(k_render<NF, false, F, true, false>);
             case RenderKernel::SLOTS2: return launch(k_render_slots<2, NF, F>);
             default: return launch(k_render_slots<4, NF, F>);  // SLOTS4 (SLOTS4_WO at NF = 48 / 96: above)
             }

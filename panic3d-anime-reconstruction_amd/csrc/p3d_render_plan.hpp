@@ -184,6 +184,48 @@ static inline int p3d_render_wide_rows(int rng, const void* jitter, const void* 
 #endif
 }
 
+// ---- interior taps (k_render with the early-outs; every other kernel keeps the generic gather set-up)
+// triplane_crop masks by position, and k_render's early-outs decode a lane only when its sample is not cropped: a decoded sample
+// has |p.x| <= crop_limit and |p.z| <= crop_limit.  Where that keeps all four bilinear taps of the x and of the z axis inside the
+// plane, the gather set-up (p3d_decode.hpp, INTERIOR) needs no range test on those axes and one address serves a texel's
+// neighbours; only the y axis, which nothing crops, keeps its tests.  The launch decides once, here, from the kernel's own chain
+//     q = p * coord_scale;  ix = (q + 1) * half - 0.5          (binary32, no contraction: p3d_tap_offsets)
+// evaluated at p = -crop_limit and p = +crop_limit: the nw tap floor(ix) must be >= 0 at the one and the se tap floor(ix) + 1 <= W - 1
+// at the other.  With coord_scale > 0 and half > 0 every operation of the chain (a product with a positive constant, a sum with a
+// constant, floor) is monotone non-decreasing in p under round-to-nearest, so the two ends bound every |p| <= crop_limit.  That
+// is an argument about the operations; tests/test_interior_taps_cpu.py adds a sweep of the chain around both ends and across the
+// interval (a sweep, not a proof).  W == H lets the three planes share one chain per axis.
+// -DP3D_INTERIOR_TAPS=0 rebuilds the library without the interior form; P3D_FLAG_GENERIC_TAPS switches it off per launch (tests, A/B).
+#ifndef P3D_INTERIOR_TAPS
+#define P3D_INTERIOR_TAPS 1
+#endif
+static inline float p3d_tap_coord(float p, float coord_scale, float half) {
+    const float q = p * coord_scale;
+    const float s = q + 1.0f;
+    const float m = s * half;
+    return m - 0.5f;
+}
+static inline bool p3d_render_interior_taps(int H, int W, const p3d_opts& o) {
+#if P3D_INTERIOR_TAPS
+    if (!(o.flags & P3D_FLAG_CROP) || (o.flags & P3D_FLAG_GENERIC_TAPS)) return false;
+    if (!(o.coord_scale > 0.0f) || !(o.crop_limit >= 0.0f) || W != H || W < 2) return false;
+    const float half = 0.5f * (float)W;
+    const float lo = __builtin_floorf(p3d_tap_coord(-o.crop_limit, o.coord_scale, half));
+    const float hi = __builtin_floorf(p3d_tap_coord(o.crop_limit, o.coord_scale, half));
+    return lo >= 0.0f && hi + 1.0f <= (float)(W - 1);  // (false for a NaN anywhere)
+#else
+    (void)H; (void)W; (void)o;
+    return false;
+#endif
+}
+// ... and of the kernels the plan can choose, the ones that have the interior form: k_render with the early-outs, except the
+// LDS-resident 96-key instantiation (per-ray limits, disparity spacing), whose registers the interior set-up would push from two
+// waves per SIMD's worth to one's (227 + 32 accumulation registers; tools/resource_usage.py)
+constexpr bool p3d_render_nf_has_interior(int NF, bool TCG) { return NF != 96 || TCG; }
+static inline bool p3d_render_plan_has_interior(const RenderPlan& pl) {
+    return (pl.kernel == RenderKernel::EARLY && p3d_render_nf_has_interior(pl.nf, false)) || pl.kernel == RenderKernel::EARLY_TCG;
+}
+
 static inline size_t p3d_render_plan_workspace_bytes(int N) {
     return 256 + (size_t)(N > 0 ? N : 0) * 8;  // global min / max + decode-step count, then one min / max pair per view
 }

@@ -303,7 +303,8 @@ def render(planes_nhwc, rays_o, rays_d, jitter, u, mlp, opts, ray_tile_w=0, dump
     """ImportanceRenderer.forward (renderer.py:162-264) with the two random draws passed in:
     jitter [N,R,Sc(,1)] (torch.rand_like, :324) and u [N*R,Sf] (torch.rand, :371).
     Returns (feat [N,R,32], depth [N,R,1], wsum [N,R,1], xyz [N,R,3]) (+ dict of per-stage dumps).
-    `stats`: pass a dict to receive the number of decode steps the launch executed (exact early-outs, see k_render).
+    `stats`: pass a dict to receive the number of decode steps the launch executed (exact early-outs, see k_render) and which
+    gather set-up it ran (`interior_taps`, include/panic3d_hip.h p3d_render_taps_info).
     per_view_clamp: clamp each image's depth to its own sample range (N batched views = N calls of the reference).
     ray_limits: (ray_start, ray_end) per ray [N,R(,1)] for rendering_options['ray_start'] == ['ray_end'] == 'auto'
     (renderer.py:165-171; cameras.ray_limits_box + cameras.patch_ray_limits compute them).
@@ -383,6 +384,10 @@ def render(planes_nhwc, rays_o, rays_d, jitter, u, mlp, opts, ray_tile_w=0, dump
         slots, tiles, full = render_plan_info(N, R, ray_tile_w, opts, dm is not None, rs_t is not None)[:3]
         kind = {1: None, 2: "pair", 4: "quad"}[slots]  # samples per wave-step, of 32 // slots rays each
         stats.update(decode_steps=steps, decode_steps_full=full, tiles=tiles, small_launch_kernel=kind is not None, small_launch_kind=kind)
+        # which gather set-up the launch ran: the interior form (crop keeps the x / z taps inside the planes) or the generic one
+        taps = L.p3d_render_taps_info(N, H, W, R, int(ray_tile_w or 0), C.byref(opts), int(dm is not None), int(rs_t is not None))
+        _lib.check(min(taps, 0), "p3d_render_taps_info")
+        stats.update(interior_taps=taps == 1)
     if weights_only:  # (feat / xyz may have been left unwritten)
         return None, depth, wsum, None
     return (feat, depth, wsum, xyz, d) if dumps else (feat, depth, wsum, xyz)

@@ -7,7 +7,7 @@ A decode step is straight-line code, so each of its parts is one basic block: a 
 is a density decode (gather + fold + transpose + layer 1 + softplus + sigma row), one with 32 MFMAs and ~450 the colour part (layer 2 +
 sigmoids).  Prints, per block with at least `--min-mfma` MFMAs: its label, the VALU / MFMA / SALU / VMEM / LDS counts and the opcodes
 (encoding suffixes _e32 / _e64 stripped, _dpp and _sdwa kept).  With a second file the same kernel's blocks of both are printed side
-by side, matched in program order, with the difference per opcode.
+by side, matched in program order, with the difference per opcode (`--other-kernel NAME`: under another name there).
 """
 import argparse
 import collections
@@ -58,10 +58,13 @@ def main():
     ap.add_argument("kernel")
     ap.add_argument("other", nargs="?")
     ap.add_argument("--min-mfma", type=int, default=16)
+    ap.add_argument("--other-kernel", help="the kernel's name in OTHER.s where it differs (a template parameter added or chosen differently)")
     ap.add_argument("-o", "--out")
     a = ap.parse_args()
-    sides = [[b for b in kernel_blocks(p, a.kernel) if classes(b[1])["MFMA"] >= a.min_mfma] for p in ([a.isa, a.other] if a.other else [a.isa])]
-    out = [f"# {a.kernel}: basic blocks with >= {a.min_mfma} MFMAs, in program order" + (f"; left {a.isa}, right {a.other}" if a.other else "")]
+    files = [(a.isa, a.kernel), (a.other, a.other_kernel or a.kernel)] if a.other else [(a.isa, a.kernel)]
+    sides = [[b for b in kernel_blocks(p, k) if classes(b[1])["MFMA"] >= a.min_mfma] for p, k in files]
+    out = [f"# {a.kernel}: basic blocks with >= {a.min_mfma} MFMAs, in program order" +
+           (f"; left {a.isa}, right {a.other}" + (f" ({a.other_kernel})" if a.other_kernel else "") if a.other else "")]
     if a.other and len(sides[0]) != len(sides[1]):
         out.append(f"# block counts differ ({len(sides[0])} / {len(sides[1])}): matched in order as far as they go")
     for i in range(max(len(s) for s in sides)):
