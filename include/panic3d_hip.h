@@ -73,6 +73,9 @@ extern "C" {
 #define P3D_FLAG_GENERIC_TAPS 131072 /* p3d_render_f32, a TEST SWITCH: k_render keeps the generic gather set-up (every tap range-tested and
                                       * addressed on its own) also where the launch's crop would let it take the interior form
                                       * (p3d_render_interior_taps, csrc/p3d_render_plan.hpp).  Same bits either way: tests, A/B timing. */
+#define P3D_FLAG_SERIAL_MERGE 262144 /* p3d_render_f32, a TEST SWITCH: k_render's merge pre-pass walks the merged list step by step
+                                      * (p3d_merge_bits_half) also in the instantiation that otherwise finds the merged positions by rank
+                                      * search (csrc/p3d_importance.hpp).  Same bits and the same decode steps either way: tests, A/B timing. */
 #define P3D_FLAG_SHARED_PLANES 64 /* planes holds ONE image [1][3][H][W][32] shared by all N batches of rays / points (many
                                     views of one subject in one launch; the reference would pass planes.expand(N, ...)) */
 

@@ -14,6 +14,7 @@ P3D_FLAG_PAIR16 = 16384
 P3D_FLAG_QUAD8 = 32768
 P3D_FLAG_WEIGHTS_ONLY = 65536
 P3D_FLAG_GENERIC_TAPS = 131072  # test switch: k_render keeps the generic gather set-up (include/panic3d_hip.h)
+P3D_FLAG_SERIAL_MERGE = 262144  # test switch: k_render's merge pre-pass by the serial walk (include/panic3d_hip.h)
 P3D_MAX_S = 192
 P3D_ABI_VERSION = 9  # include/panic3d_hip.h; lib() refuses a library built for another version
 

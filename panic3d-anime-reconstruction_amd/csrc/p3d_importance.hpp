@@ -11,12 +11,15 @@
 //               Sf/2 + i in register i, half 0 with MINUS rank Sf/2 - 1 - i (p3d_half_rank / the sign are applied by the store);
 //   merge       the stable merge of the coarse and the fine column is cut at merged position S/2 (p3d_merge_split finds how many
 //               coarse samples lie in front of the cut); half h walks [h * S/2, ...) and the bit words are OR-ed across halves.
+//               Or, without the serial walk (p3d_merge_ranks_half): half h finds the merged positions of half of the coarse
+//               ranks, each by a search in the sorted fine column, eight searches in flight.
 //
 // The networks only move values (min / max of finite floats; a negation is exact), so the sorted column — and with it every
 // result — is the one any correct sort gives.  The schedules are templates over the key type and its operations, so a host
 // program can run the very schedules on 0-1 inputs, 64 of them per machine word (tests/importance_split_host.cpp); the block at
 // the end (under __HIPCC__) holds the pieces that need the lanes of a wave and is device only.
 #pragma once
+#include <stdint.h>
 
 #if defined(__HIPCC__)
 #define P3D_IMP_FN __host__ __device__ __forceinline__
@@ -153,6 +156,112 @@ P3D_IMP_FN void p3d_merge_bits_half(RD rd, KN known, PUT put, int Sc, int Sf, in
     }
 }
 
+// The merge pre-pass by RANK SEARCH (the counterpart of p3d_merge_bits_half): coarse rank i lands at merged position
+// i + #{fine < t_i} (ties: coarse first), and the count comes from a binary search in the sorted fine column fine(k), eight ranks in
+// flight — the searches of a batch do not depend on one another, where every step of the serial merge waits for the read before
+// it.  NF is the capacity of the fine column (Sf <= NF): the search runs the steps 2^r .. 1, 2^r the largest power of two <= NF
+// (NF = 48: six rounds, 96: seven, 0: none), and a bit row over the merged list is NW words (Sc + Sf <= 32 * NW).
+// -DP3D_MERGE_RANKS=0 keeps every kernel that has a coarse column on the serial merge (the A/B of DESIGN.md section 6).
+#ifndef P3D_MERGE_RANKS
+#define P3D_MERGE_RANKS 1
+#endif
+P3D_IMP_FN constexpr int p3d_rank_first_step(int NF) { return p3d_pow2_ceil(NF + 1) >> 1; }
+// Half h's share: the coarse ranks [h * Sch, (h + 1) * Sch), Sch = Sc / 2 rounded up to whole batches of eight.  tc_sorted(i): the
+// coarse depth of sorted rank i; known(i, t): coarse rank i at depth t needs no decode (asked for ranks up to 2 * Sch - 1; the answer
+// for a rank >= Sc is dropped).  Out, in registers: the bits of ITS ranks in the is-coarse row slw and in the known row knw; the two
+// halves' rows OR-ed are the whole is-coarse row and the coarse samples' part of the known row.  And, for the fine samples' part where
+// their crop bits are two runs (P3dFineRuns): fine rank k sits at merged position k + #{coarse i : pos_i <= k} (coarse i lies in front
+// of it unless fine k < t_i, that is unless k < pos_i), so the half also counts its ranks in front of the fine ranks fr.k1 and fr.k2.
+struct P3dFineRuns {
+    int k1, k2;  // in: the fine ranks [0, k1) and [k2, Sf) are cropped, the ranks between them are not
+    int n1, n2;  // out: the half's coarse ranks in front of fine rank k1 / of fine rank k2 (the two halves' counts add up)
+};
+template <int NF, int NW, typename TCS, typename FINE, typename KN>
+P3D_IMP_FN void p3d_merge_ranks_half(TCS tc_sorted, FINE fine, KN known, uint32_t (&slw)[NW], uint32_t (&knw)[NW], P3dFineRuns& fr, int Sc, int Sf,
+                                     int h) {
+P3D_IMP_UNROLL
+    for (int w = 0; w < NW; ++w) { slw[w] = 0u; knw[w] = 0u; }
+    fr.n1 = 0; fr.n2 = 0;
+    const int Sch = ((Sc + 15) >> 4) << 3, ib = h * Sch;
+    for (int i0 = 0; i0 < Sch; i0 += 8) {
+        float tv[8];
+        int pos[8];
+P3D_IMP_UNROLL
+        for (int q = 0; q < 8; ++q) { tv[q] = tc_sorted(ib + i0 + q < Sc ? ib + i0 + q : Sc - 1); pos[q] = 0; }
+P3D_IMP_UNROLL
+        for (int step = p3d_rank_first_step(NF); step >= 1; step >>= 1) {
+            float c[8];
+P3D_IMP_UNROLL
+            for (int q = 0; q < 8; ++q) c[q] = fine((pos[q] + step <= Sf) ? pos[q] + step - 1 : 0);
+P3D_IMP_UNROLL
+            for (int q = 0; q < 8; ++q) pos[q] = ((pos[q] + step <= Sf) && (c[q] < tv[q])) ? pos[q] + step : pos[q];
+        }
+P3D_IMP_UNROLL
+        for (int q = 0; q < 8; ++q) {
+            const int i = ib + i0 + q;
+            const bool kn = known(i, tv[q]);
+            const int P = i + pos[q], pw = (i < Sc) ? (P >> 5) : -1;  // (a rank past the end sets no bit)
+            const uint32_t b = 1u << (P & 31);
+P3D_IMP_UNROLL
+            for (int w = 0; w < NW; ++w) {
+                slw[w] |= (pw == w) ? b : 0u;
+                knw[w] |= (pw == w && kn) ? b : 0u;
+            }
+            fr.n1 += (i < Sc && pos[q] <= fr.k1) ? 1 : 0;
+            fr.n2 += (i < Sc && pos[q] <= fr.k2) ? 1 : 0;
+        }
+    }
+}
+// The fine samples' crop bits fw (bit k: sorted fine sample k is cropped; at most 64 of them) as two runs, one at each end of the
+// column: k1, k2 as in P3dFineRuns; false if the bits are anything else.  A crop by position along a ray gives such runs wherever the
+// uncropped part of the ray is one stretch — the kernel does not rely on it: it asks, and deposits bit by bit otherwise.
+template <int NFW>
+P3D_IMP_FN bool p3d_fine_runs(const uint32_t (&fw)[NFW], int Sf, int& k1, int& k2) {
+    static_assert(NFW <= 2, "the bits in one 64-bit word");
+    const uint64_t F = (uint64_t)fw[0] | (NFW > 1 ? (uint64_t)fw[NFW - 1] << 32 : 0ull);
+    const uint64_t all = Sf >= 64 ? ~0ull : ((1ull << Sf) - 1ull);
+    if ((F & all) == all) { k1 = Sf; k2 = Sf; return (F & ~all) == 0ull; }  // every fine sample (Sf = 0: none there is)
+    k1 = __builtin_ctzll(~F);                       // F has a zero below bit Sf
+    const uint64_t top = ~(F << (64 - Sf)) ;        // bit 63: fine rank Sf - 1, zeros shifted in below
+    const int tail = __builtin_clzll(top);          // top != 0: that zero again
+    k2 = Sf - tail;
+    return __builtin_popcountll(F) == k1 + tail;
+}
+// The fine samples' part of the known row from the runs: fine rank k1 sits at merged position P1 = k1 + (coarse ranks in front of it)
+// and k2 at P2 likewise (a rank Sf: at S); the fine samples in front of P1 and from P2 on are the cropped ones.
+template <int NW>
+P3D_IMP_FN void p3d_deposit_fine_runs(const uint32_t (&slw)[NW], uint32_t (&knw)[NW], int P1, int P2, int S) {
+P3D_IMP_UNROLL
+    for (int w = 0; w < NW; ++w) {
+        const int lo = 32 * w;
+        const uint32_t below1 = P1 >= lo + 32 ? ~0u : (P1 <= lo ? 0u : (1u << (P1 - lo)) - 1u);  // merged positions < P1
+        const uint32_t below2 = P2 >= lo + 32 ? ~0u : (P2 <= lo ? 0u : (1u << (P2 - lo)) - 1u);
+        const uint32_t inlist = S >= lo + 32 ? ~0u : (S <= lo ? 0u : (1u << (S - lo)) - 1u);
+        knw[w] |= ~slw[w] & (below1 | ~below2) & inlist;
+    }
+}
+// ... and the fine samples' part of the known row: sorted fine sample k sits at the k-th zero of the (whole) is-coarse row, and bit
+// k of the words fw says that it is cropped.  Walks the S merged positions and ORs the bits into knw.
+template <int NW, int NFW>
+P3D_IMP_FN void p3d_deposit_fine_bits(const uint32_t (&slw)[NW], uint32_t (&knw)[NW], const uint32_t (&fw)[NFW], int S) {
+    int fk = 0;
+P3D_IMP_UNROLL
+    for (int w = 0; w < NW; ++w) {
+        if (w * 32 < S) {  // wave-uniform
+            uint32_t kk = 0u;
+            for (int b = 0; b < 32; ++b) {
+                const bool isf = !((slw[w] >> b) & 1u) && (w * 32 + b < S);
+                uint32_t fwv = fw[NFW - 1];
+P3D_IMP_UNROLL
+                for (int x = NFW - 2; x >= 0; --x) fwv = (fk < 32 * (x + 1)) ? fw[x] : fwv;
+                kk |= (isf && ((fwv >> (fk & 31)) & 1u)) ? (1u << b) : 0u;
+                fk += isf ? 1 : 0;
+            }
+            knw[w] |= kk;
+        }
+    }
+}
+
 #if defined(__HIPCC__)
 // ---- device only: the pieces of the split that need the lanes of a wave
 // The sort of the split (see the top of this file): in, half h's H = Sf/2 draws; out, half 1 holds rank H + i in register i,
@@ -206,65 +315,30 @@ __device__ __forceinline__ float p3d_coarse_rank(RAW raw, int i, int Sc, bool wa
     return a;
 }
 
-// The merge pre-pass without a coarse column (TCG; p3d_merge_bits_half is its counterpart with one): coarse rank i lands at merged
-// position i + #{fine < t_i} (ties: coarse first), found by a search in the sorted fine column fine(k), eight ranks in flight; half
-// h searches the coarse ranks [h * Sch, (h + 1) * Sch).  The two bit rows are built in registers (six words each: Sc + Sf <= 192), OR-ed
-// across the halves and handed to put(word, kw, sw) once.  known(i, t): coarse rank i at depth t needs no decode; fw0-2: sorted fine
-// sample k is cropped — fine k sits at the k-th zero of the is-coarse row.
-template <typename TCS, typename FINE, typename KN, typename PUT>
-__device__ __forceinline__ void p3d_merge_bits_ranks(TCS tc_sorted, FINE fine, KN known, PUT put, uint32_t fw0, uint32_t fw1, uint32_t fw2,
-                                                     int Sc, int Sf, int h) {
+// The whole pre-pass by rank search (above) on a wave: half h searches its ranks, the two halves' rows are OR-ed with one lane
+// exchange per word, the fine samples' crop bits fw (NFW words over the sorted fine column) are deposited — skipped where no ray of
+// the wave has one; from their two runs where every ray's bits are runs, bit by bit otherwise — and every word of the two rows is
+// handed to put(word, kw, sw) once: nothing to zero, no OR in memory.  k_render's TCG instantiations (no coarse column: tc_sorted
+// recomputes the depth) and, with a column in LDS, its 48-key kernel.
+template <int NF, int NW, int NFW, typename TCS, typename FINE, typename KN, typename PUT>
+__device__ __forceinline__ void p3d_merge_bits_ranks(TCS tc_sorted, FINE fine, KN known, PUT put, const uint32_t (&fw)[NFW], int Sc, int Sf, int h) {
     const int S = Sc + Sf, nmw = (S + 31) >> 5;
-    uint32_t slw[6], knw[6];
+    uint32_t slw[NW], knw[NW];
+    P3dFineRuns fr = {0, 0, 0, 0};
+    bool runs = false;  // every ray of the wave has its cropped fine samples in two runs (asked where the bits fit 64: the 48-key kernel)
+    if constexpr (NFW <= 2) runs = __builtin_amdgcn_ballot_w64(!p3d_fine_runs(fw, Sf, fr.k1, fr.k2)) == 0;
+    p3d_merge_ranks_half<NF, NW>(tc_sorted, fine, known, slw, knw, fr, Sc, Sf, h);
 P3D_IMP_UNROLL
-    for (int w = 0; w < 6; ++w) { slw[w] = 0u; knw[w] = 0u; }
-    const int Sch = ((Sc + 15) >> 4) << 3, ib = h * Sch;
-    for (int i0 = 0; i0 < Sch; i0 += 8) {
-        float tv[8];
-        int pos[8];
+    for (int w = 0; w < NW; ++w) { slw[w] |= __shfl_xor(slw[w], 32); knw[w] |= __shfl_xor(knw[w], 32); }  // the other half's ranks
+    uint32_t any = 0u;
 P3D_IMP_UNROLL
-        for (int q = 0; q < 8; ++q) { tv[q] = tc_sorted(ib + i0 + q < Sc ? ib + i0 + q : Sc - 1); pos[q] = 0; }
-P3D_IMP_UNROLL
-        for (int step = 64; step >= 1; step >>= 1) {
-            float c[8];
-P3D_IMP_UNROLL
-            for (int q = 0; q < 8; ++q) c[q] = fine((pos[q] + step <= Sf) ? pos[q] + step - 1 : 0);
-P3D_IMP_UNROLL
-            for (int q = 0; q < 8; ++q) pos[q] = ((pos[q] + step <= Sf) && (c[q] < tv[q])) ? pos[q] + step : pos[q];
-        }
-P3D_IMP_UNROLL
-        for (int q = 0; q < 8; ++q) {
-            const int i = ib + i0 + q;
-            const bool kn = known(i, tv[q]);
-            const int P = i + pos[q], pw = (i < Sc) ? (P >> 5) : -1;  // (a rank past the end sets no bit)
-            const uint32_t b = 1u << (P & 31);
-P3D_IMP_UNROLL
-            for (int w = 0; w < 6; ++w) {
-                slw[w] |= (pw == w) ? b : 0u;
-                knw[w] |= (pw == w && kn) ? b : 0u;
-            }
-        }
+    for (int x = 0; x < NFW; ++x) any |= fw[x];
+    if (__builtin_amdgcn_ballot_w64(any != 0u) != 0) {
+        if (runs) p3d_deposit_fine_runs(slw, knw, fr.k1 + fr.n1 + __shfl_xor(fr.n1, 32), fr.k2 + fr.n2 + __shfl_xor(fr.n2, 32), S);
+        else p3d_deposit_fine_bits(slw, knw, fw, S);
     }
 P3D_IMP_UNROLL
-    for (int w = 0; w < 6; ++w) { slw[w] |= __shfl_xor(slw[w], 32); knw[w] |= __shfl_xor(knw[w], 32); }  // the other half's ranks
-    if (__builtin_amdgcn_ballot_w64((fw0 | fw1 | fw2) != 0u) != 0) {
-        int fk = 0;
-P3D_IMP_UNROLL
-        for (int w = 0; w < 6; ++w) {
-            if (w * 32 < S) {  // wave-uniform
-                uint32_t kk = 0u;
-                for (int b = 0; b < 32; ++b) {
-                    const bool isf = !((slw[w] >> b) & 1u) && (w * 32 + b < S);
-                    const uint32_t fwv = (fk < 32) ? fw0 : (fk < 64 ? fw1 : fw2);
-                    kk |= (isf && ((fwv >> (fk & 31)) & 1u)) ? (1u << b) : 0u;
-                    fk += isf ? 1 : 0;
-                }
-                knw[w] |= kk;
-            }
-        }
-    }
-P3D_IMP_UNROLL
-    for (int w = 0; w < 6; ++w)
+    for (int w = 0; w < NW; ++w)
         if (w < nmw) put(w, knw[w], slw[w]);
 }
 

@@ -395,7 +395,10 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
     bool wave_bad = false;       //      ... somewhere in this wave
     auto tc_sorted = [&](int i) -> float { return p3d_coarse_rank(tc_raw, i, Sc, wave_unsorted, wave_bad); };
     uint32_t mw0 = 0u, mw1 = 0u, mw2 = 0u;  // TCG: known-masked bits of coarse samples 0-31 / 32-63 / 64-95 (registers, not LDS rows)
-    uint32_t fw0 = 0u, fw1 = 0u, fw2 = 0u;  // TCG: sorted fine sample k is cropped (sigma = -1000 by position)
+    uint32_t fw[3] = {0u, 0u, 0u};  // TCG, RANKS: sorted fine sample k is cropped (sigma = -1000 by position)
+    // RANKS: the 48-key kernel with the early-outs runs its merge pre-pass by rank search (p3d_importance.hpp) where the merged list
+    // is at most 96 samples (the launch decides: Sc <= 48)
+    constexpr bool RANKS = P3D_MERGE_RANKS && EARLY && !TCG && NF == 48;
     const bool dump = DUMP && active && h == 0;
 
     // ---- stratified depths (TCG: made in the coarse pass, never stored)
@@ -573,18 +576,25 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
             const int row0 = p3d_half_rank(H, h, 0), rstep = h ? 1 : -1;
             const uint32_t neg0 = h ? 0u : 0x80000000u;  // half 0 holds its keys negated
             uint64_t crop = 0ull;  // TCG: bit i = the key of register i is cropped
+            uint32_t crop24 = 0u;  // RANKS: the same (H <= 32 keys)
 #pragma unroll
             for (int i = 0; i < H; ++i) {
                 const float v = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tf[i]) ^ neg0);
                 tfA[(row0 + rstep * i) * 32 + j] = v;
                 if constexpr (TCG) crop |= cx.cropped_at(v) ? (1ull << i) : 0ull;
+                else if constexpr (RANKS) crop24 |= cx.cropped_at(v) ? (1u << i) : 0u;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             if constexpr (TCG) {  // register i -> rank: half 1 shifts by H, half 0 mirrors; then each half takes the other's bits
                 static_assert(H >= 32 && H < 64, "the 96 rank bits as 64 + 32");
                 const uint64_t g0 = h ? (crop << H) : (__builtin_bitreverse64(crop) >> (64 - H));
-                fw0 = (uint32_t)g0; fw1 = (uint32_t)(g0 >> 32); fw2 = h ? (uint32_t)(crop >> (64 - H)) : 0u;
-                fw0 |= __shfl_xor(fw0, 32); fw1 |= __shfl_xor(fw1, 32); fw2 |= __shfl_xor(fw2, 32);
+                fw[0] = (uint32_t)g0; fw[1] = (uint32_t)(g0 >> 32); fw[2] = h ? (uint32_t)(crop >> (64 - H)) : 0u;
+                fw[0] |= __shfl_xor(fw[0], 32); fw[1] |= __shfl_xor(fw[1], 32); fw[2] |= __shfl_xor(fw[2], 32);
+            } else if constexpr (RANKS) {  // the same with 2 * H <= 64 rank bits
+                static_assert(H <= 32, "a half's bits in one word, the rank bits in two");
+                const uint64_t g0 = h ? ((uint64_t)crop24 << H) : (uint64_t)(__builtin_bitreverse32(crop24) >> (32 - H));
+                fw[0] = (uint32_t)g0; fw[1] = (uint32_t)(g0 >> 32);
+                fw[0] |= __shfl_xor(fw[0], 32); fw[1] |= __shfl_xor(fw[1], 32);
             }
         } else if constexpr (NF > 0) {  // the padded capacity (NF = 64): both halves do all of it
             // (the same text as k_render_slots' below, on purpose: behind one shared helper every LDS read of the searches got one
@@ -627,7 +637,7 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
                     tfA[i * 32 + j] = tf[i];  // over the cdf rows: every search is done
                     if constexpr (TCG) {
                         const uint32_t b = cx.cropped_at(tf[i]) ? (1u << (i & 31)) : 0u;
-                        if (i < 32) fw0 |= b; else if (i < 64) fw1 |= b; else fw2 |= b;
+                        if (i < 32) fw[0] |= b; else if (i < 64) fw[1] |= b; else fw[2] |= b;
                     }
                 }
         } else {
@@ -692,32 +702,52 @@ __global__ __launch_bounds__(64 * P3D_RENDER_WAVES, p3d_render_occ(NF, TCG)) voi
         };
         float tcn = 0.0f;  // TCG: the head of the coarse list, tc_sorted(min(ci, Sc - 1)), fetched ahead of its use
         if constexpr (TCG) {
-            p3d_merge_bits_ranks(
+            p3d_merge_bits_ranks<96, 6>(
                 tc_sorted, [&](int k) { return tfA[k * 32 + j]; },
                 [&](int i, float t) {
                     const uint32_t mwv = (i < 32) ? mw0 : (i < 64 ? mw1 : mw2);
                     return cx.cropped_at(t) || ((mwv >> (i & 31)) & 1u);
                 },
-                [&](int w, uint32_t kw, uint32_t sw) { knA[w * 32 + j] = kw; slA[w * 32 + j] = sw; }, fw0, fw1, fw2, Sc, Sf, h);
+                [&](int w, uint32_t kw, uint32_t sw) { knA[w * 32 + j] = kw; slA[w * 32 + j] = sw; }, fw, Sc, Sf, h);
             tcn = tc_sorted(0);
         } else
         if constexpr (EARLY) {
             // the merge, once: bit q of slA = merged sample q is the head of the coarse list, bit q of knA = its sigma is known
-            // Half 0 walks the merged positions [0, S/2), half 1 [S/2, S), starting behind the samples that lie in front of the
-            // cut (p3d_importance.hpp).  The word that holds the cut gets bits from both halves, so the rows start at zero and
-            // take their words by LDS OR.
-            for (int w = 0; w < nmw; ++w) { knA[w * 32 + j] = 0u; slA[w * 32 + j] = 0u; }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            p3d_merge_bits_half(
-                [&](bool c, int i) { return (c ? tcA : tfA)[i * 32 + j]; },
-                [&](bool c, int i, float t) {
-                    bool known = cx.cropped_at(t);
-                    if (c && Sf > 0) known = known || ((mkA[(i >> 5) * 32 + j] >> (i & 31)) & 1u);  // Sf == 0: no coarse pass ran
-                    return known;
-                },
-                [&](int w, uint32_t kw, uint32_t sw) { atomicOr(&knA[w * 32 + j], kw); atomicOr(&slA[w * 32 + j], sw); },
-                Sc, Sf, h);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            bool by_ranks = false;
+            if constexpr (RANKS) {
+                // By rank search (p3d_importance.hpp): the coarse column is sorted by now, the coarse pass's known-masked bits are
+                // read per rank from their rows, the fine samples' crop bits come from the sort's store, and both halves store
+                // every word of the two rows once, the same value: nothing to zero, no OR in LDS, and each lane reads back only
+                // what it stored itself.
+                by_ranks = S <= 96 && !p.serial_merge;  // launch-uniform: three words per row; the flag is a test switch
+                if (by_ranks) {
+                    const uint32_t fwr[2] = {fw[0], fw[1]};
+                    p3d_merge_bits_ranks<48, 3>(
+                        [&](int i) { return tcA[i * 32 + j]; }, [&](int k) { return tfA[k * 32 + j]; },
+                        [&](int i, float t) {
+                            const int ic = i < Sc ? i : Sc - 1;
+                            return cx.cropped_at(t) || ((mkA[(ic >> 5) * 32 + j] >> (ic & 31)) & 1u);
+                        },
+                        [&](int w, uint32_t kw, uint32_t sw) { knA[w * 32 + j] = kw; slA[w * 32 + j] = sw; }, fwr, Sc, Sf, h);
+                }
+            }
+            if (!by_ranks) {
+                // Serially: half 0 walks the merged positions [0, S/2), half 1 [S/2, S), starting behind the samples that lie in
+                // front of the cut (p3d_importance.hpp).  The word that holds the cut gets bits from both halves, so the rows start
+                // at zero and take their words by LDS OR.
+                for (int w = 0; w < nmw; ++w) { knA[w * 32 + j] = 0u; slA[w * 32 + j] = 0u; }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                p3d_merge_bits_half(
+                    [&](bool c, int i) { return (c ? tcA : tfA)[i * 32 + j]; },
+                    [&](bool c, int i, float t) {
+                        bool known = cx.cropped_at(t);
+                        if (c && Sf > 0) known = known || ((mkA[(i >> 5) * 32 + j] >> (i & 31)) & 1u);  // Sf == 0: no coarse pass ran
+                        return known;
+                    },
+                    [&](int w, uint32_t kw, uint32_t sw) { atomicOr(&knA[w * 32 + j], kw); atomicOr(&slA[w * 32 + j], sw); },
+                    Sc, Sf, h);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
             ci = 0;  // from here on: coarse samples among the first m merged ones (the fine index is m - ci)
         }
         P3D_PHASE(P3D_PH_MERGE);
@@ -1600,6 +1630,7 @@ static int render_impl(const float* planes, int N, int H, int W, const float* ra
     p.planes = planes; p.rays_o = rays_o; p.rays_d = rays_d; p.jitter = jitter; p.u = u;
     p.rng = rng; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
     p.wide_rows = p3d_render_wide_rows(rng, jitter, u, Sc, Sf);
+    p.serial_merge = (opts->flags & P3D_FLAG_SERIAL_MERGE) ? 1 : 0;
     p.w0 = w0; p.b0 = b0; p.w1 = w1; p.b1 = b1;
     p.out_feat = out_feat; p.out_depth = out_depth; p.out_wsum = out_wsum; p.out_xyz = out_xyz;
     p.gminmax = (uint32_t*)workspace;

@@ -35,6 +35,7 @@ struct RenderParams {
     int rng;          // p3d_render_rng_f32: the two draws come from the counter-based generator of include/p3d_numerics.h
     uint32_t seed_lo, seed_hi;
     int wide_rows;    // k_render: P3D_WIDE_JITTER | P3D_WIDE_U, the rows it may load as 16-byte pieces (p3d_render_wide_rows)
+    int serial_merge;  // P3D_FLAG_SERIAL_MERGE: k_render's merge pre-pass walks the merged list also where it would search by rank
     P3dTileOrder order;  // k_render: the XCD tile order (p3d_render_plan.hpp)
     P3dDecodeCfg cfg;
 };
